@@ -10,22 +10,28 @@ batched get_rows over the rank's slice, device-resident row ids -> CSR in HBM,
 plus (N > 1) the RCCL all-gatherv that reassembles the global CSR on every
 rank (pipelined: step k's exchange overlaps step k+1's traversal).
 
-Prints ONE JSON line (rank 0).
+A plain run sets up, warms up, times the steps and prints ONE JSON line
+(rank 0): the headline figure and what the timed steps themselves measured.
+--dump-outputs DIR also writes the CSR of the last timed step as .npy files.
+Everything below that takes runs of its own is measured only with --full.
   roofline  -- the dominant kernel's layout-true algorithmic bytes per launch
                (what its layout must read and write: alg_basis) / its
                HIP-event-timed average duration (achieved) / the 8 TB/s spec
                (frac); beside it the measured HBM traffic (rocprofv3 --pmc
                FETCH_SIZE and WRITE_SIZE, one child pass each over this same
-               workload, at N = 1 before the timed run: traffic,
+               workload, at N = 1 before the timed run, --full: traffic,
                traffic_frac), SURVEY §8(d)'s probe-equivalent bytes
                (64 B x V + 16 + 4 B x L per row, V and L counted exactly on
                the device), and the measured ceilings: a streaming read and
-               random 64-byte requests (tools/probe.hip).
+               random 64-byte requests (tools/probe.hip).  A plain run
+               fills in only what the timed steps give: the kernel's
+               HIP-event time there and its algorithmic bytes.
   cpu_baseline -- the oracle's restatement of BRWT::get_row on the same
                structure (built on the host from the same spec), on a bounded
-               row sample, on the job's host cores and single-threaded.
+               row sample, on the job's host cores and single-threaded
+               (--full).
   parity    -- the whole global batch's CSR against the oracle, element-wise
-               and by a 64-bit hash (N = 1 and, on rank 0, N > 1).
+               and by a 64-bit hash (N = 1 and, on rank 0, N > 1; --full).
 """
 from __future__ import annotations
 
@@ -124,8 +130,17 @@ def parse():
     ap.add_argument("--traffic-out", default="", help="write the live traffic summary (JSON) here")
     ap.add_argument("--no-probe", action="store_true", help="skip the measured ceilings")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (host buffers) leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what takes runs of its own: the roofline's "
+                         "live traffic, isolated kernel time, work counts and measured ceilings, the CPU baseline "
+                         "and parity against the host oracle, the end-to-end leg, the no-gather steps (N > 1); "
+                         "--traffic, --no-probe, --no-cpu, --no-e2e select among them")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the CSR the last timed step returned to DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--pmc-pass", action="store_true", help=argparse.SUPPRESS)  # child under rocprofv3
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     w = WORKLOADS[a.workload]
     for k in ("rows", "cols", "density", "batch", "layout"):
         if getattr(a, k) is None:
@@ -257,6 +272,45 @@ def csr_hash(off: np.ndarray, cols: np.ndarray) -> str:
     h.update(np.ascontiguousarray(off, dtype=np.uint64).tobytes())
     h.update(np.ascontiguousarray(cols, dtype=np.uint32).tobytes())
     return h.hexdigest()
+
+
+DUMP_SAMPLE_ROWS = 1 << 19   # rows of a larger batch that are written
+DUMP_MAX_LABELS = 8 << 20    # labels written (32 MB as float32)
+
+
+def dump_outputs(out_dir, off_t, cols_t, seed):
+    """--dump-outputs: the CSR the last timed step returned (offsets off_t
+    [rows + 1], labels cols_t[:offsets[-1]]; device tensors) as
+    out_dir/<name>.npy, so that two builds can be compared output for output.
+    The whole CSR where it is small; of a larger batch a fixed sample of rows
+    (a seeded choice that depends on the batch size alone, the leading rows
+    of it whose labels fit DUMP_MAX_LABELS): under 64 MB in all.
+      num_labels.npy    f64 [1]  offsets[-1] of the whole batch
+      sample_rows.npy   f64 [S]  positions in the batch of the rows written
+      row_offsets.npy   f64 [S]  their CSR offsets (exact: < 2^53)
+      label_counts.npy  f32 [S]  their label counts
+      labels.npy        f32 [sum of the counts]  their labels, row after row"""
+    n = off_t.numel() - 1
+    if n > DUMP_SAMPLE_ROWS:
+        sel = np.random.default_rng(seed).choice(n, DUMP_SAMPLE_ROWS, replace=False).astype(np.int64)
+    else:
+        sel = np.arange(n, dtype=np.int64)
+    sel_t = torch.from_numpy(sel).to(off_t.device)
+    starts = off_t[sel_t].cpu().numpy().astype(np.int64)
+    counts = off_t[sel_t + 1].cpu().numpy().astype(np.int64) - starts
+    keep = int(np.searchsorted(np.cumsum(counts), DUMP_MAX_LABELS, side="right"))
+    sel, starts, counts = sel[:keep], starts[:keep], counts[:keep]
+    # positions in the label array of the kept rows' labels, row after row
+    pos = np.repeat(starts - (np.cumsum(counts) - counts), counts) + np.arange(int(counts.sum()), dtype=np.int64)
+    labels = cols_t[torch.from_numpy(pos).to(cols_t.device)].cpu().numpy().view(np.uint32)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"num_labels": np.array([int(off_t[-1].item())], dtype=np.float64),
+              "sample_rows": sel.astype(np.float64), "row_offsets": starts.astype(np.float64),
+              "label_counts": counts.astype(np.float32), "labels": labels.astype(np.float32)}
+    assert sum(v.nbytes for v in arrays.values()) <= 64 << 20
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    log(f"wrote {len(sel):,} rows, {len(labels):,} labels of the last timed step to {out_dir}")
 
 
 def probe_ceilings(dev_t, stream_ptr, free_bytes, struct_bytes=64 << 30):
@@ -392,7 +446,7 @@ def main():
     # their own copy of the structure
     kernel_re = None
     traffic = None
-    if rank == 0 and world == 1 and a.traffic != "off":
+    if a.full and rank == 0 and world == 1 and a.traffic != "off":
         if a.layout in ("rows", "both") and a.kernel == 0:
             kernel_re = "k_traverse_rows|k_var_decode"
         else:
@@ -635,7 +689,9 @@ def main():
         glob_off, glob_cols = last_off, last_cols[:n_lab]
     chk = min(a.check_rows, G) if a.check_rows > 0 else G
     have_global = world == 1 or gather
-    if rank == 0 and have_global:
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, glob_off, glob_cols, a.seed)
+    if a.full and rank == 0 and have_global:
         off_h = glob_off[: chk + 1].cpu().numpy().view(np.uint64)
         cols_h = glob_cols[: int(off_h[-1])].cpu().numpy().view(np.uint32)
     if gather:
@@ -647,7 +703,7 @@ def main():
     # alone (one context, one stream, untimed for `value`) is reported
     # beside the roofline as `isolated`
     iso = None
-    if Q >= 2:
+    if a.full and Q >= 2:
         for _ in range(3):
             mat.get_rows_device_async(rows_ts[0], off_t, cols_t, status_t, sptr)
         torch.cuda.synchronize()
@@ -668,7 +724,7 @@ def main():
     # right after, so the driver's SCALE lines carry both curves (VERDICT r05
     # #4); `value` stays the gathered figure (SURVEY §8(e)'s contract)
     no_gather = None
-    if world > 1 and gather:
+    if a.full and world > 1 and gather:
         for q in range(Q):
             qstatus[q].zero_()
         torch.cuda.synchronize()
@@ -702,15 +758,17 @@ def main():
 
     # measured ceilings of this GPU (streaming read; random 64-/128-B requests)
     stream_gbs = rnd = None
-    if rank == 0 and not a.no_probe:
+    if a.full and rank == 0 and not a.no_probe:
         free, _ = torch.cuda.mem_get_info(dev_t)
         stream_gbs, rnd = probe_ceilings(dev_t, sptr, free, struct_bytes)
 
     # exact work accounting for the algorithmic roofline (untimed diagnostic pass)
-    try:
-        visits, labels = mat.count_work_device(rows_t, sptr)
-    except L.MBRWTError:  # terminal records (--rows-code 2) store no internal masks: no V accounting
-        visits, labels = None, n_lab
+    visits, labels = None, n_lab
+    if a.full:
+        try:
+            visits, labels = mat.count_work_device(rows_t, sptr)
+        except L.MBRWTError:  # terminal records (--rows-code 2) store no internal masks: no V accounting
+            pass
     assert labels == n_lab, (labels, n_lab)
     # SURVEY §8(d)'s per-row figure: 64 B per index-bit probe of the
     # reference recursion (BRWT.cpp:30) + row id + offset + 4 B per label --
@@ -730,7 +788,7 @@ def main():
 
     cpu = None
     parity = None
-    if rank == 0 and have_global and not a.no_cpu:
+    if a.full and rank == 0 and have_global and not a.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle as O  # CPU baseline and parity legs only
 
@@ -795,7 +853,7 @@ def main():
 
     # the drop-in path end to end (host ids -> host CSR), N = 1, rank 0
     e2e = None
-    if rank == 0 and world == 1 and have_global and not a.no_e2e:
+    if a.full and rank == 0 and world == 1 and have_global and not a.no_e2e:
         dev_hash = csr_hash(off_h, cols_h)
         e2e = end_to_end(mat, np.ascontiguousarray(rows_global[:chk]), int(off_h[-1]), dev_t, dev_hash)
         e2e["scope"] = (f"the bench's batch {last_k} ({chk:,} rows) through mbrwt_get_rows; csr_hash compared with the "
@@ -908,6 +966,7 @@ def main():
         "n_gpus": world,
         "steps": a.steps,
         "warmup": a.warmup,
+        "full": a.full,
         "ms_per_step": elapsed / a.steps * 1e3,
         "higher_is_better": True,
         "scaling": a.scaling,

@@ -42,16 +42,32 @@ uint64_t count_ones(const uint64_t *w, uint64_t size) {
     return c;
 }
 
-// hipMalloc + copy of a host image; large images are page-locked for the
-// copy (pageable copies of freshly built images measured ~0.3 GB/s)
+// hipMalloc + copy of a host image; large images go through a page-locked
+// staging buffer of the runtime's own (pageable copies of freshly built
+// images measured ~0.3 GB/s).  The image itself is not page-locked in place:
+// it is heap memory whose pages it shares with other vectors, and
+// registering and unregistering such ranges beside the runtime's own pinning
+// of pageable copies left later copies of neighbouring vectors faulting.
 hipError_t upload_bytes(const void *src, size_t bytes, void **out) {
     void *d = nullptr;
     hipError_t e = hipMalloc(&d, bytes);
     if (e != hipSuccess) return e;
-    void *h = const_cast<void *>(src);
-    const bool reg = bytes >= (1u << 20) && hipHostRegister(h, bytes, hipHostRegisterDefault) == hipSuccess;
-    e = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
-    if (reg) (void)hipHostUnregister(h);
+    constexpr size_t kStage = 32u << 20;
+    void *stage = nullptr;
+    if (bytes >= (1u << 20) && hipHostMalloc(&stage, std::min(bytes, kStage), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        stage = nullptr;
+    }
+    if (stage) {
+        for (size_t off = 0; off < bytes && e == hipSuccess; off += kStage) {
+            const size_t nb = std::min(kStage, bytes - off);
+            std::memcpy(stage, static_cast<const char *>(src) + off, nb);
+            e = hipMemcpy(static_cast<char *>(d) + off, stage, nb, hipMemcpyHostToDevice);
+        }
+        (void)hipHostFree(stage);
+    } else {
+        e = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
+    }
     if (e != hipSuccess) {
         (void)hipFree(d);
         return e;

@@ -1,5 +1,6 @@
-// Compiled (syntax and template instantiation only) against the REFERENCE's
-// own common/annotate.hpp by tests/test_reference_headers.py: with
+// Compiled (syntax and template instantiation only) against the mirror's
+// restated interface by tests/test_reference_headers.py, and against the
+// REFERENCE's own common/annotate.hpp where a checkout of it is at hand: with
 // MBRWT_WITH_REFERENCE_ANNOTATE the mirror's static annotator derives from
 // the reference's annotate::MultiLabelEncoded and implements every pure
 // virtual of it, so the reference's AnnotatedDBG can hold it unchanged.

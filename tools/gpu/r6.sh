@@ -9,7 +9,7 @@ mkdir -p gpurun_out
 HB=$!
 trap 'kill $HB 2>/dev/null' EXIT
 PYT="python -u -m pytest -v --timeout 300 --timeout-method thread"
-B="python -u bench.py --no-e2e --no-probe --traffic off"
+B="python -u bench.py --full --no-e2e --no-probe --traffic off"
 for STAGE in "$@"; do
 O=gpurun_out/r6_$STAGE; mkdir -p $O
 case "$STAGE" in
@@ -17,7 +17,7 @@ rows)  # the row-record GPU tests + host pipeline + classes
   timeout -k 10 700 $PYT tests/test_gpu_rows.py tests/test_gpu_hostpipe.py tests/test_gpu_classes.py > $O/pytest_rows.log 2>&1
   ;;
 trace)  # C4 bench (live PMC, ceilings) and the kernel trace of its two-stream timed region
-  timeout -k 10 400 python -u bench.py --no-cpu --no-e2e --traffic-out $O/traffic_c4.json > $O/bench_c4.log 2>&1 &&
+  timeout -k 10 400 python -u bench.py --full --no-cpu --no-e2e --traffic-out $O/traffic_c4.json > $O/bench_c4.log 2>&1 &&
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_c4 -o run --output-format csv -- python -u bench.py --no-cpu --no-e2e --no-probe --traffic off --steps 50 > $O/bench_c4_under_rocprof.log 2>&1 &&
   python tools/trace_overlap.py $(find $O/prof_c4 -name "*kernel_trace.csv" | head -1) > $O/overlap.json 2>&1
   ;;
@@ -26,13 +26,13 @@ greedy)  # the greedy + relax shape at 3.7 B rows: the automatic block shape and
   ;;
 nib)  # nibble-coded records: the row-record tests, C4 with nibble codes (parity) and bytes (A/B)
   timeout -k 10 700 $PYT tests/test_gpu_rows.py tests/test_gpu_classes.py tests/test_gpu_files.py > $O/pytest_rows.log 2>&1 &&
-  timeout -k 10 400 python -u bench.py --no-e2e --traffic off --rows-code 1 > $O/bench_c4_nib.log 2>&1 &&
+  timeout -k 10 400 python -u bench.py --full --no-e2e --traffic off --rows-code 1 > $O/bench_c4_nib.log 2>&1 &&
   timeout -k 10 200 $B --no-cpu --rows-code 0 > $O/bench_c4_byte.log 2>&1 &&
   timeout -k 10 200 $B --no-cpu --rows-code 1 > $O/bench_c4_nib2.log 2>&1
   ;;
 nib2)  # nibble decode with one 4-byte LDS read: the nibble tests, C4 nibble (parity) / byte A/B
   timeout -k 10 700 $PYT tests/test_gpu_rows.py -k "nibble or odometer or async or errors" > $O/pytest_rows.log 2>&1 &&
-  timeout -k 10 400 python -u bench.py --no-e2e --traffic off --rows-code 1 > $O/bench_c4_nib.log 2>&1 &&
+  timeout -k 10 400 python -u bench.py --full --no-e2e --traffic off --rows-code 1 > $O/bench_c4_nib.log 2>&1 &&
   timeout -k 10 200 $B --no-cpu --rows-code 0 > $O/bench_c4_byte.log 2>&1 &&
   timeout -k 10 200 $B --no-cpu --rows-code 1 > $O/bench_c4_nib2.log 2>&1
   ;;
@@ -63,7 +63,7 @@ final_slow)  # 2/3: the full-size parity cases (C3, C4, C5, rows >= 2^32)
   timeout -k 10 1100 $PYT tests -m "gpu and slow" -x > $O/pytest_gpu_slow.log 2>&1
   ;;
 final_bench)  # 3/3: bench.py (whole-batch parity, CPU baseline, live PMC), its kernel trace + stats
-  timeout -k 10 400 python -u bench.py --traffic-out $O/traffic_c4.json > $O/bench_c4.log 2>&1 &&
+  timeout -k 10 400 python -u bench.py --full --traffic-out $O/traffic_c4.json > $O/bench_c4.log 2>&1 &&
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_c4 -o run --output-format csv -- python -u bench.py --no-cpu --no-e2e --no-probe --traffic off > $O/bench_c4_under_rocprof.log 2>&1
   ;;
 greedy_sq)  # SQ / TA counters of the greedy + relax traversal at 3.7 B rows (three passes, r05's C4 sets)
@@ -73,11 +73,11 @@ greedy_sq)  # SQ / TA counters of the greedy + relax traversal at 3.7 B rows (th
   timeout -s KILL 400 rocprofv3 --pmc GRBM_COUNT GRBM_GUI_ACTIVE SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_SCA SQ_INSTS_SMEM SQ_INST_CYCLES_VMEM_WR TA_BUFFER_WAVEFRONTS_sum TA_TA_BUSY_sum -d $O/sq3 -o run --output-format csv -- $G > $O/sq3.log 2>&1
   ;;
 rehearsal)  # bench.py's N > 1 step on the final sources: two ranks on one GPU over gloo, 1 B rows (two images fit)
-  timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 --dist-backend gloo --rows 1000000000 --steps 10 --warmup 3 --no-e2e > $O/rehearsal_2rank.log 2>&1
+  timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29531 bench.py --full --gpus 2 --dist-backend gloo --rows 1000000000 --steps 10 --warmup 3 --no-e2e > $O/rehearsal_2rank.log 2>&1
   ;;
 term)  # terminal records: their tests, C4 with them (parity) and ABAB against bytes, the greedy shape with both
   timeout -k 10 500 $PYT tests/test_gpu_rows.py -k "terminal or nibble or odometer or async or errors or compact_cus" > $O/pytest_rows.log 2>&1 &&
-  timeout -k 10 300 python -u bench.py --no-e2e --no-probe --traffic off --rows-code 2 > $O/bench_c4_term_parity.log 2>&1 &&
+  timeout -k 10 300 python -u bench.py --full --no-e2e --no-probe --traffic off --rows-code 2 > $O/bench_c4_term_parity.log 2>&1 &&
   timeout -k 10 200 $B --no-cpu --rows-code 0 > $O/bench_c4_byte_1.log 2>&1 &&
   timeout -k 10 200 $B --no-cpu --rows-code 2 > $O/bench_c4_term_1.log 2>&1 &&
   timeout -k 10 200 $B --no-cpu --rows-code 0 > $O/bench_c4_byte_2.log 2>&1 &&
@@ -93,7 +93,7 @@ final_rest)  # the files after a first failure in test_gpu_rows.py, smoke, then 
   timeout -k 10 900 $PYT tests -m "gpu and slow" > $O/pytest_gpu_slow.log 2>&1
   ;;
 term3)  # C4 terminal records at three rows per block (the compact image) against the cost model's two, ABAB
-  timeout -k 10 300 python -u bench.py --no-e2e --no-probe --traffic off --rows-block 64:3 > $O/bench_c4_s3_parity.log 2>&1 &&
+  timeout -k 10 300 python -u bench.py --full --no-e2e --no-probe --traffic off --rows-block 64:3 > $O/bench_c4_s3_parity.log 2>&1 &&
   timeout -k 10 200 $B --no-cpu > $O/bench_c4_s2_1.log 2>&1 &&
   timeout -k 10 200 $B --no-cpu --rows-block 64:3 > $O/bench_c4_s3_1.log 2>&1 &&
   timeout -k 10 200 $B --no-cpu > $O/bench_c4_s2_2.log 2>&1 &&
@@ -109,7 +109,7 @@ prefetch)  # terminal walk reading the next field's words early: tests, then ABA
   # (needs tools/_ab/libmbrwt_head.so: the previous commit's libmbrwt.so, copied there before the change)
   H="env MBRWT_LIB=tools/_ab/libmbrwt_head.so"
   timeout -k 10 400 $PYT tests/test_gpu_rows.py -k "terminal or async or errors or reference_grids or random_matrices or compact_cus" > $O/pytest_rows.log 2>&1 &&
-  timeout -k 10 300 python -u bench.py --no-e2e --no-probe --traffic off > $O/bench_c4_parity.log 2>&1 &&
+  timeout -k 10 300 python -u bench.py --full --no-e2e --no-probe --traffic off > $O/bench_c4_parity.log 2>&1 &&
   timeout -k 10 200 $H $B --no-cpu > $O/bench_c4_head_1.log 2>&1 &&
   timeout -k 10 200 $B --no-cpu > $O/bench_c4_new_1.log 2>&1 &&
   timeout -k 10 200 $H $B --no-cpu > $O/bench_c4_head_2.log 2>&1 &&
@@ -124,8 +124,8 @@ c4_sq)  # SQ / TA counters of the C4 traversal with terminal records (r05's thre
   timeout -s KILL 400 rocprofv3 --pmc GRBM_COUNT GRBM_GUI_ACTIVE SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_SCA SQ_INSTS_SMEM SQ_INST_CYCLES_VMEM_WR TA_BUFFER_WAVEFRONTS_sum TA_TA_BUSY_sum -d $O/sq3 -o run --output-format csv -- $C > $O/sq3.log 2>&1
   ;;
 configs)  # BASELINE configs[1] (C2) and configs[2] (C3) on HEAD: whole-batch parity, live PMC
-  timeout -k 10 400 python -u bench.py --workload c2 --no-e2e > $O/bench_c2.log 2>&1 &&
-  timeout -k 10 600 python -u bench.py --workload c3 --no-e2e > $O/bench_c3.log 2>&1
+  timeout -k 10 400 python -u bench.py --full --workload c2 --no-e2e > $O/bench_c2.log 2>&1 &&
+  timeout -k 10 600 python -u bench.py --full --workload c3 --no-e2e > $O/bench_c3.log 2>&1
   ;;
 c2ab)  # C2 (cache-resident) with terminal records against byte masks, ABAB
   timeout -k 10 200 $B --workload c2 --no-cpu --rows-code 3 > $O/bench_c2_byte_1.log 2>&1 &&
