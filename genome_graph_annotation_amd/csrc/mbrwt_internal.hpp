@@ -384,7 +384,7 @@ struct Ctx {
     // options
     bool timing = false;
     uint32_t slot_labels = 0;           // 0 = auto
-    int kernel_variant = 0;             // MBRWT_OPT_KERNEL (0 = default = 5)
+    int kernel_variant = 0;             // MBRWT_OPT_KERNEL: 0 the default families, 1 the lane-per-row node kernel
     int rows_walk = 0;                  // MBRWT_OPT_ROWS_WALK (6: the non-odometer walk on uniform trees)
     int64_t test_fail_chunk = -1;       // MBRWT_OPT_TEST_FAIL_CHUNK (test hook: host_get_rows fails at that chunk)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -396,9 +396,8 @@ struct Ctx {
     hipEvent_t ev_trav = nullptr, ev_comp = nullptr;
     double timing_ms = 0;
     uint64_t timing_launches = 0;
-    int grid_cache = 0;
-    // launch geometry of the last rowblock kernel (query.hip): the occupancy
-    // query and the LDS attribute are host calls paid once, not per batch
+    // launch geometry of the last rowblock kernel (resident_workgroups): the
+    // occupancy query and the LDS attribute are host calls paid once, not per batch
     const void *rb_fn = nullptr;
     size_t rb_lds = 0;
     uint32_t rb_threads = 0;
@@ -494,6 +493,21 @@ int hip_fail(hipError_t e, const char *what);
     } while (0)
 
 int ensure(Workspace &w, size_t bytes);
+// plumbing of the get_rows drivers (query.hip, rows.hip, rows_var.hip; defined in query.hip)
+// *blocks = the workgroups of `fn` (`threads` threads, `lds` bytes of dynamic
+// LDS) resident on the device, at most occ_cap per CU (0 = no cap); owns Ctx::rb_*
+int resident_workgroups(Ctx &c, const void *fn, uint32_t threads, size_t lds, int occ_cap, uint64_t *blocks);
+// the event pair around the call's traversal kernel: ev0 / ev1, or (timing on,
+// asynchronous call) a pair of its own that mbrwt_take_timing sums
+int timing_events(Ctx &c, bool async, hipEvent_t *e0, hipEvent_t *e1);
+// end of a synchronous call: d_scalars to the host, the stream synchronised,
+// the kernel time (ev0..ev1) taken, the status mapped to a return code + message
+//   row-record block {total, status}; `fallback`: the message of any other status
+int finish_rows_call(Ctx &c, uint64_t *needed, const char *fallback, hipStream_t s);
+//   node-image block {total, overflow rows, error bits}
+int finish_nodes_call(Ctx &c, uint64_t cap, uint64_t *needed, uint64_t *overflow, hipStream_t s);
+// the node protocol's error bits: 1 -> MBRWT_ERR_RANGE, 2 -> MBRWT_ERR_UNSUPPORTED (+ *msg for set_error)
+int node_error_code(uint64_t bits, const char **msg = nullptr);
 
 // image construction (image.cpp / synth.hip)
 int build_from_desc(const mbrwt_tree_desc &desc, int device, Tree &tree);

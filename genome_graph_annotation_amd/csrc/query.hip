@@ -361,22 +361,27 @@ __global__ __launch_bounds__(256) void k_traverse(TravParams p) {
 // reference's output order); the index of the next child comes from lane
 // c's register through a cross-lane shuffle.
 // ------------------------------------------------------------------------
-template <int MAXD, int CPL, typename MaskT>
+// children per lane, one 16-byte read per visit (4: 12.1 against 11.1 ms, profiles/r01/exp_c3_refseq_sweep.log)
+constexpr int kGroupCpl = 2;
+// waves per SIMD asked of the register allocator (none: 11.5 against 11.1 ms, profiles/r01/exp_c3_refseq_sweep.log)
+constexpr int kGroupWpe = 8;
+
+template <int MAXD, typename MaskT>
 struct GroupFrames {
-    uint32_t jc[MAXD][CPL];  // per lane: position of child c*CPL+k in its own image
+    uint32_t jc[MAXD][kGroupCpl];  // per lane: position of child c*kGroupCpl+k in its own image
     uint32_t fc[MAXD];       // uniform: dnode of child 0
     MaskT pend[MAXD];        // uniform: children still to take (bit i = child i)
     int sp;
-    __device__ __forceinline__ void push(const uint32_t (&j)[CPL], uint32_t f, MaskT p) {
+    __device__ __forceinline__ void push(const uint32_t (&j)[kGroupCpl], uint32_t f, MaskT p) {
 #pragma unroll
         for (int k = MAXD - 1; k > 0; --k) {
 #pragma unroll
-            for (int q = 0; q < CPL; ++q) jc[k][q] = jc[k - 1][q];
+            for (int q = 0; q < kGroupCpl; ++q) jc[k][q] = jc[k - 1][q];
             fc[k] = fc[k - 1];
             pend[k] = pend[k - 1];
         }
 #pragma unroll
-        for (int q = 0; q < CPL; ++q) jc[0][q] = j[q];
+        for (int q = 0; q < kGroupCpl; ++q) jc[0][q] = j[q];
         fc[0] = f;
         pend[0] = p;
         ++sp;
@@ -385,7 +390,7 @@ struct GroupFrames {
 #pragma unroll
         for (int k = 0; k < MAXD - 1; ++k) {
 #pragma unroll
-            for (int q = 0; q < CPL; ++q) jc[k][q] = jc[k + 1][q];
+            for (int q = 0; q < kGroupCpl; ++q) jc[k][q] = jc[k + 1][q];
             fc[k] = fc[k + 1];
             pend[k] = pend[k + 1];
         }
@@ -441,17 +446,15 @@ struct GroupSink {
     }
 };
 
-// spread the low G bits of x to every CPL-th bit position
-template <int CPL>
+// spread the low G bits of x to every kGroupCpl-th bit position
 __device__ __forceinline__ uint64_t spread_bits(uint64_t x, uint32_t G) {
-    if constexpr (CPL == 1) return x;
     uint64_t r = 0;
-    for (uint32_t i = 0; i < G; ++i) r |= ((x >> i) & 1ull) << (i * CPL);
+    for (uint32_t i = 0; i < G; ++i) r |= ((x >> i) & 1ull) << (i * kGroupCpl);
     return r;
 }
 
-template <int MAXD, int CPL, typename MaskT, int MODE, bool NT = false>
-__device__ __forceinline__ void group_visit(const TravParams &p, GroupFrames<MAXD, CPL, MaskT> &st, GroupSink<MODE> &sk,
+template <int MAXD, typename MaskT, int MODE>
+__device__ __forceinline__ void group_visit(const TravParams &p, GroupFrames<MAXD, MaskT> &st, GroupSink<MODE> &sk,
                                             const NodeInfo &nd, uint32_t j, uint32_t c, uint32_t gbase,
                                             uint64_t gmask, uint32_t G) {
     const uint32_t a = nd.arity;
@@ -476,7 +479,7 @@ __device__ __forceinline__ void group_visit(const TravParams &p, GroupFrames<MAX
                 const NodeInfo nb = decode(gld(cn + 2 * wb), gld(cn + 2 * wb + 1));
                 if constexpr (MODE == MODE_WORK) sk.visits += nb.arity;
                 const uint32_t lm = pb.byte(o2++);
-                if (A / CPL == c) {
+                if (A / kGroupCpl == c) {
                     uint32_t r = total;
                     for (uint32_t mm = lm; mm; mm &= mm - 1) sk.put(p, r++, nb.label + (uint32_t)__builtin_ctz(mm));
                 }
@@ -500,7 +503,7 @@ __device__ __forceinline__ void group_visit(const TravParams &p, GroupFrames<MAX
                 const NodeInfo ch = decode(gld(reinterpret_cast<const uint64_t *>(p.cnodes) + 2 * (nd.first_child + k)),
                                            gld(reinterpret_cast<const uint64_t *>(p.cnodes) + 2 * (nd.first_child + k) + 1));
                 if constexpr (MODE == MODE_WORK) sk.visits += ch.arity;
-                if (k / CPL == c) {
+                if (k / kGroupCpl == c) {
                     uint32_t mm = m, r = before;
                     for (; mm; mm &= mm - 1) sk.put(p, r++, ch.label + (uint32_t)__builtin_ctz(mm));
                 }
@@ -515,32 +518,26 @@ __device__ __forceinline__ void group_visit(const TravParams &p, GroupFrames<MAX
     if (nd.kind == KIND_PLANE) {
         const uint32_t t = j & 31;
         const uint32_t below = (1u << t) - 1u;
-        uint32_t bit[CPL], jc[CPL];
+        uint32_t bit[kGroupCpl], jc[kGroupCpl];
 #pragma unroll
-        for (int q = 0; q < CPL; ++q) {
+        for (int q = 0; q < kGroupCpl; ++q) {
             bit[q] = 0;
             jc[q] = 0;
         }
-        if (c * CPL < a) {
-            const uint64_t blk = base + (uint64_t)(j >> 5) * nd.stride + 8u * CPL * c;
-            uint32_t rk[CPL], bw[CPL];
-            if constexpr (CPL == 1) {
-                const uint2 rb = gld_at_nt<uint2, NT>(blk);
-                rk[0] = rb.x;
-                bw[0] = rb.y;
-            } else {
+        if (c * kGroupCpl < a) {
+            const uint64_t blk = base + (uint64_t)(j >> 5) * nd.stride + 8u * kGroupCpl * c;
+            uint32_t rk[kGroupCpl], bw[kGroupCpl];
 #pragma unroll
-                for (int h = 0; h < CPL / 2; ++h) {
-                    const uint4 q4 = gld_at_nt<uint4, NT>(blk + 16 * h);
-                    rk[2 * h] = q4.x;
-                    bw[2 * h] = q4.y;
-                    rk[2 * h + 1] = q4.z;
-                    bw[2 * h + 1] = q4.w;
-                }
+            for (int h = 0; h < kGroupCpl / 2; ++h) {
+                const uint4 q4 = gld_at<uint4>(blk + 16 * h);
+                rk[2 * h] = q4.x;
+                bw[2 * h] = q4.y;
+                rk[2 * h + 1] = q4.z;
+                bw[2 * h + 1] = q4.w;
             }
 #pragma unroll
-            for (int q = 0; q < CPL; ++q) {
-                if (c * CPL + q < a) {
+            for (int q = 0; q < kGroupCpl; ++q) {
+                if (c * kGroupCpl + q < a) {
                     bit[q] = (bw[q] >> t) & 1u;
                     jc[q] = rk[q] + (uint32_t)__builtin_popcount(bw[q] & below);  // rank1(j) - 1
                 }
@@ -548,7 +545,7 @@ __device__ __forceinline__ void group_visit(const TravParams &p, GroupFrames<MAX
         }
         uint64_t P = 0;
 #pragma unroll
-        for (int q = 0; q < CPL; ++q) P |= spread_bits<CPL>((__ballot(bit[q]) >> gbase) & gmask, G) << q;
+        for (int q = 0; q < kGroupCpl; ++q) P |= spread_bits((__ballot(bit[q]) >> gbase) & gmask, G) << q;
         if (P) {
             if (st.sp >= MAXD) {
                 if (c == 0) atomicOr(&p.scalars[2], 2ull);
@@ -559,13 +556,13 @@ __device__ __forceinline__ void group_visit(const TravParams &p, GroupFrames<MAX
         return;
     }
     uint64_t m;  // all children are leaves: one mask per position (uniform load)
-    if (nd.kind == KIND_MASK8) m = gld_at_nt<uint8_t, NT>(base + j);
+    if (nd.kind == KIND_MASK8) m = gld_at<uint8_t>(base + j);
     else if (nd.kind == KIND_MASK16) m = gld_at<uint16_t>(base + 2ull * j);
     else if (nd.kind == KIND_MASK32) m = gld_at<uint32_t>(base + 4ull * j);
     else m = gld_at<uint64_t>(base + 8ull * j);
 #pragma unroll
-    for (int q = 0; q < CPL; ++q) {
-        const uint32_t cc = c * CPL + q;
+    for (int q = 0; q < kGroupCpl; ++q) {
+        const uint32_t cc = c * kGroupCpl + q;
         if (cc < a && ((m >> cc) & 1u)) {
             const uint32_t label =
                 (nd.flags & FLAG_CONSEC_LABELS) ? nd.label + cc
@@ -577,8 +574,8 @@ __device__ __forceinline__ void group_visit(const TravParams &p, GroupFrames<MAX
     sk.cnt += (uint32_t)__builtin_popcountll(m);
 }
 
-template <int MAXD, int CPL, typename MaskT, int MODE, int WPE, bool NT = false>
-__global__ __launch_bounds__(256, WPE) void k_traverse_group(TravParams p, uint32_t G) {
+template <int MAXD, typename MaskT, int MODE>
+__global__ __launch_bounds__(256, kGroupWpe) void k_traverse_group(TravParams p, uint32_t G) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t c = lane & (G - 1);
     const uint32_t gbase = lane & ~(G - 1);
@@ -587,11 +584,11 @@ __global__ __launch_bounds__(256, WPE) void k_traverse_group(TravParams p, uint3
     const uint64_t gstride = (uint64_t)gridDim.x * groups_per_block;
     uint64_t s = (uint64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
 
-    GroupFrames<MAXD, CPL, MaskT> st;
+    GroupFrames<MAXD, MaskT> st;
 #pragma unroll
     for (int k = 0; k < MAXD; ++k) {
 #pragma unroll
-        for (int q = 0; q < CPL; ++q) st.jc[k][q] = 0;
+        for (int q = 0; q < kGroupCpl; ++q) st.jc[k][q] = 0;
         st.fc[k] = 0;
         st.pend[k] = 0;
     }
@@ -626,7 +623,7 @@ __global__ __launch_bounds__(256, WPE) void k_traverse_group(TravParams p, uint3
             return;
         }
         const NodeInfo nd = node_info(0);
-        group_visit<MAXD, CPL, MaskT, MODE, NT>(p, st, sk, nd, (uint32_t)row, c, gbase, gmask, G);
+        group_visit<MAXD, MaskT, MODE>(p, st, sk, nd, (uint32_t)row, c, gbase, gmask, G);
         if constexpr (MODE == MODE_WORK) {
             // folded root: its own probe counts once, its children's only if its bit is set
             if (p.folded) sk.visits = sk.visits + 1 - ((st.sp == 0 && sk.cnt == 0) ? (uint64_t)nd.arity : 0ull);
@@ -669,16 +666,16 @@ __global__ __launch_bounds__(256, WPE) void k_traverse_group(TravParams p, uint3
             const uint32_t w = st.fc[0] + cs;
             uint32_t mine = st.jc[0][0];
 #pragma unroll
-            for (int q = 1; q < CPL; ++q)
-                if ((cs % CPL) == (uint32_t)q) mine = st.jc[0][q];
-            const uint32_t jw = (uint32_t)__shfl((int)mine, (int)(gbase + cs / CPL), 64);
+            for (int q = 1; q < kGroupCpl; ++q)
+                if ((cs % kGroupCpl) == (uint32_t)q) mine = st.jc[0][q];
+            const uint32_t jw = (uint32_t)__shfl((int)mine, (int)(gbase + cs / kGroupCpl), 64);
             if (P == 0) st.pop();  // no children left at this level: drop it before descending
             const NodeInfo nd = node_info(w);
             if (nd.kind == KIND_LEAF) {
                 if (c == 0) sk.put(p, 0, nd.label);
                 sk.cnt += 1;
             } else {
-                group_visit<MAXD, CPL, MaskT, MODE, NT>(p, st, sk, nd, jw, c, gbase, gmask, G);
+                group_visit<MAXD, MaskT, MODE>(p, st, sk, nd, jw, c, gbase, gmask, G);
             }
         }
     }
@@ -1295,24 +1292,31 @@ __global__ __launch_bounds__(256, 8) void k_traverse_p2w(P2wParams p) {
 //                 table in LDS and writes the labels -- in pre-order, the
 //                 reference's order -- into the wave's ring;
 //   flush      -- p2w's: 64-label units as full-line stores.
-// MAXD: stack levels of the walk (>= the PACKT subtrees' height); WPB: waves
-// per workgroup (the PTW table is staged once per workgroup).
+// MAXD: stack levels of the walk (>= the PACKT subtrees' height).  The temp
+// labels are u16 (PTW columns are < 2^15).
 // ------------------------------------------------------------------------
-template <bool WIDE, uint32_t RING = 512>
+// waves per workgroup (one staged PTW table each): 3 x 7 per CU, 2.27 against 2.47 ms at 4 x 4
+// (profiles/r02/v42_bench_greedy_ptw_wpb7.log)
+constexpr uint32_t kPtwWpb = 7;
+// labels of a wave's ring: the size at which 21 waves' LDS fits a CU (the same profile; 512 with 4-wave workgroups)
+constexpr uint32_t kPtwRing = 256;
+using PtwLabel = uint16_t;  // the temp region's labels
+
+template <bool WIDE>
 struct PtwLayout {
     static constexpr uint32_t kItems = WIDE ? 256 : 128;  // 16 rows x R children
-    static constexpr uint32_t kRing = RING;               // labels
+    static constexpr uint32_t kRing = kPtwRing;           // labels
     // items j | items k | row counts | group's first item | blocks (64 x 64 B) | ring
     static constexpr uint32_t kWords = kItems + kItems / 4 + 16 + 20 + 1024 + kRing;
 };
 
 // the labels of a KIND_PACKT record (masks from byte o on) into the ring
 // (or, `direct`, the rowblock's temp region) from label position pos on
-template <int MAXD, typename LT>
+template <int MAXD>
 __device__ __forceinline__ void ptw_walk(const AS_LDS uint8_t *pb, uint32_t o, uint32_t node,
                                          const AS_LDS uint32_t *ntab, const AS_LDS uint16_t *etab,
                                          AS_LDS uint32_t *ring, uint32_t smask, uint32_t pos, bool direct,
-                                         LT *out, uint32_t C, bool &overflow) {
+                                         PtwLabel *out, uint32_t C, bool &overflow) {
     uint32_t nw = ntab[node];
     uint32_t m = pb[o++];
     if ((nw >> 24) > 8) m |= (uint32_t)pb[o++] << 8;
@@ -1336,7 +1340,7 @@ __device__ __forceinline__ void ptw_walk(const AS_LDS uint8_t *pb, uint32_t o, u
         if (e & 0x8000u) {
             const uint32_t label = e & 0x7FFFu;
             if (!direct) ring[pos & smask] = label;
-            else if (pos < C) gst(out + pos, (LT)label);
+            else if (pos < C) gst(out + pos, (PtwLabel)label);
             ++pos;
             continue;
         }
@@ -1408,9 +1412,9 @@ __device__ __forceinline__ void ptw_walk_wave(const AS_LDS uint8_t *pb, uint32_t
     }
 }
 
-template <bool NT, bool WIDE, int MAXD, int WPB, uint32_t RING = 512, typename LT = uint32_t>
-__global__ __launch_bounds__(64 * WPB) void k_traverse_ptw(P2wParams p) {
-    using Lay = PtwLayout<WIDE, RING>;
+template <bool NT, bool WIDE, int MAXD>
+__global__ __launch_bounds__(64 * kPtwWpb) void k_traverse_ptw(P2wParams p) {
+    using Lay = PtwLayout<WIDE>;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_ptw[];
     const uint32_t lane = threadIdx.x & 63, c = lane & 3, g = lane >> 2, gb = lane & ~3u;
     const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1435,13 +1439,12 @@ __global__ __launch_bounds__(64 * WPB) void k_traverse_ptw(P2wParams p) {
     bool overflow = false;
 
     const uint64_t nblocks = (p.n + 15) / 16;
-    const uint64_t wstride = (uint64_t)gridDim.x * WPB;
-    for (uint64_t rb = (uint64_t)blockIdx.x * WPB + wv; rb < nblocks; rb += wstride) {
+    const uint64_t wstride = (uint64_t)gridDim.x * kPtwWpb;
+    for (uint64_t rb = (uint64_t)blockIdx.x * kPtwWpb + wv; rb < nblocks; rb += wstride) {
         const uint64_t r0 = rb * 16;
         const uint32_t nr = (uint32_t)(p.n - r0 < 16 ? p.n - r0 : 16);
-        // LT: the temp region's label type (u16 when every label is < 2^16:
-        // half the traversal's writes and the compaction's reads)
-        LT *const out = reinterpret_cast<LT *>(p.temp) + rb * (uint64_t)p.C;
+        // u16 temp labels: half the traversal's writes and the compaction's reads
+        PtwLabel *const out = reinterpret_cast<PtwLabel *>(p.temp) + rb * (uint64_t)p.C;
 
         // ---- root phase: the super-root's block at group g's row ----
         uint32_t row = kNone;
@@ -1568,16 +1571,16 @@ __global__ __launch_bounds__(64 * WPB) void k_traverse_ptw(P2wParams p) {
             const bool direct = rtot + (running - flushed) > Lay::kRing;
             if (direct) {
                 for (uint32_t q2 = flushed + lane; q2 < running; q2 += 64)
-                    if (q2 < p.C) gst(out + q2, (LT)ring[q2 & smask]);
+                    if (q2 < p.C) gst(out + q2, (PtwLabel)ring[q2 & smask]);
                 wave_sync_lds();
             }
             if (!direct) {
                 ptw_walk_wave<MAXD>(pb, s + 1, ent, blk, ntab, etab, ring, smask, ibase, overflow);
                 if (act && !blk) ring[ibase & smask] = ent & 0x7FFFFFFFu;
             } else if (blk) {
-                ptw_walk<MAXD, LT>(pb, s + 1, ent, ntab, etab, ring, smask, ibase, direct, out, p.C, overflow);
+                ptw_walk<MAXD>(pb, s + 1, ent, ntab, etab, ring, smask, ibase, direct, out, p.C, overflow);
             } else if (act && ibase < p.C) {
-                gst(out + ibase, (LT)(ent & 0x7FFFFFFFu));
+                gst(out + ibase, (PtwLabel)(ent & 0x7FFFFFFFu));
             }
             running += rtot;
             if (direct) {
@@ -1587,14 +1590,14 @@ __global__ __launch_bounds__(64 * WPB) void k_traverse_ptw(P2wParams p) {
                 if (F > flushed) {
                     wave_sync_lds();
                     for (uint32_t q2 = flushed + lane; q2 < F; q2 += 64)
-                        if (q2 < p.C) gst(out + q2, (LT)ring[q2 & smask]);
+                        if (q2 < p.C) gst(out + q2, (PtwLabel)ring[q2 & smask]);
                     flushed = F;
                 }
             }
             wave_sync_lds();  // the slots and the ring are reused
         }
         for (uint32_t q2 = flushed + lane; q2 < running; q2 += 64)
-            if (q2 < p.C) gst(out + q2, (LT)ring[q2 & smask]);
+            if (q2 < p.C) gst(out + q2, (PtwLabel)ring[q2 & smask]);
         if (lane < nr) gst(p.counts + r0 + lane, rowcnt[lane]);
         if (lane == 0) gst(p.block_counts + rb, running);
         if (running > p.C) {  // rowblock overflow: its rows go to the direct pass
@@ -1909,13 +1912,11 @@ template <int MODE>
 Trav pick_traverse(const Ctx &c) {
     const uint32_t depth = c.tree.stack_depth, max_arity = c.tree.max_arity;
     Trav t;
-    const int kv = c.kernel_variant;
     const bool p2 = c.tree.has_pack2;
-    if (MODE == MODE_SLOTS && c.tree.fast_shape && c.tree.lds_complete && (kv == 0 || (kv >= 17 && kv <= 23)) &&
+    if (MODE == MODE_SLOTS && c.tree.fast_shape && c.tree.lds_complete && c.kernel_variant == 0 &&
         (!p2 || (c.tree.push_frames <= 1 && !c.tree.has_mask_children))) {
-        // k_traverse_fast2; 17/18 force plain / non-temporal block reads, the
-        // default uses non-temporal reads on images larger than 1 GiB (+2.6 %)
-        const bool nt = kv == 18 || kv == 20 || (kv == 0 && c.tree.image_bytes > (1ull << 30));
+        // k_traverse_fast2, with non-temporal block reads on images larger than 1 GiB (+2.6 %)
+        const bool nt = c.tree.image_bytes > (1ull << 30);
         const bool smallk = auto_slots(c) == kStageLabels;
         t.G = 4;
         t.fast = true;
@@ -1948,26 +1949,22 @@ Trav pick_traverse(const Ctx &c) {
 #undef PICK
         return t;
     }
-    // group kernel: CPL children per lane, G = pow2ceil(ceil(max_arity / CPL)) lanes per row;
-    // variants 5/6 request a higher occupancy (waves per SIMD) from the register allocator
-    // default (and the fast variants on trees they do not fit): 2 children per lane, 8 waves/SIMD
-    const int v = (c.kernel_variant == 0 || c.kernel_variant >= 11) ? 5 : c.kernel_variant;  // 17/18: fast2 only
-    const int cpl = v == 2 ? 1 : (v == 4 || v == 6) ? 4 : 2;
-    const int wpe = (v == 5 || v == 10) ? 8 : v == 6 ? 6 : 1;  // (v == 10 past depth 8 runs as 5)
-    const uint32_t need = (max_arity + cpl - 1) / cpl;
+    // group kernel (also the other modes of fast2's trees): G = pow2ceil(ceil(max_arity / kGroupCpl)) lanes per row
+    const uint32_t need = (max_arity + kGroupCpl - 1) / kGroupCpl;
     uint32_t G = 1;
     while (G < need) G <<= 1;
     t.G = G;
-#define PICKG(D, CPLV, W)                                                                          \
-    if (depth <= D && cpl == CPLV && wpe == W) {                                                   \
-        t.group_fn = max_arity <= 32 ? (GroupFn)k_traverse_group<D, CPLV, uint32_t, MODE, W>       \
-                                     : (GroupFn)k_traverse_group<D, CPLV, uint64_t, MODE, W>;      \
+#define PICKG(D)                                                                                   \
+    if (depth <= D) {                                                                              \
+        t.group_fn = max_arity <= 32 ? (GroupFn)k_traverse_group<D, uint32_t, MODE>                \
+                                     : (GroupFn)k_traverse_group<D, uint64_t, MODE>;               \
         t.fn = reinterpret_cast<const void *>(t.group_fn);                                         \
         return t;                                                                                  \
     }
-#define PICKD(CPLV, W) PICKG(4, CPLV, W) PICKG(8, CPLV, W) PICKG(16, CPLV, W) PICKG(32, CPLV, W)
-    PICKD(2, 8)
-#undef PICKD
+    PICKG(4)
+    PICKG(8)
+    PICKG(16)
+    PICKG(32)
 #undef PICKG
     return t;
 }
@@ -1991,7 +1988,7 @@ int grid_for(const Ctx &c, const Trav &t, uint64_t n) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, t.fn, 256, lds_bytes(c, t)) != hipSuccess || per_cu <= 0)
         per_cu = 4;
     const uint64_t resident = (uint64_t)std::max(1, dev_cus) * (uint64_t)per_cu;
-    // fast: 64 groups x 8-row chunks (x 2 contexts for fast3)
+    // fast: 64 groups x 8-row chunks
     const uint64_t rows_per_block = t.fast ? 512 : 256 / t.G;
     const uint64_t need = (n + rows_per_block - 1) / rows_per_block;
     return (int)std::max<uint64_t>(1, std::min(need, resident));
@@ -2043,72 +2040,139 @@ int ensure(Workspace &w, size_t bytes) {
     return MBRWT_OK;
 }
 
-// k_traverse_p2w for this context?  Default for trees with a P2W table;
-// MBRWT_OPT_KERNEL 19 / 20 force plain / non-temporal reads (A/B; 17 / 18
-// force k_traverse_fast2).
-using P2wFn = void (*)(P2wParams);
-static P2wFn p2w_kernel(const Ctx &c) {
-    const int kv = c.kernel_variant;
-    if (c.tree.p2w_table.empty() || !c.d_p2w || !(kv == 0 || kv == 19 || kv == 20)) return nullptr;
-    const bool big = c.tree.image_bytes > (1ull << 30);
-    switch (kv) {
-    default:  // u16 temp labels when they fit (p2w_label16)
-        if (c.tree.num_columns <= 0x10000u) return big ? k_traverse_p2w<true, uint16_t> : k_traverse_p2w<false, uint16_t>;
-        return big ? k_traverse_p2w<true> : k_traverse_p2w<false>;
+int resident_workgroups(Ctx &c, const void *fn, uint32_t threads, size_t lds, int occ_cap, uint64_t *blocks) {
+    if (c.rb_fn != fn || c.rb_lds != lds || c.rb_threads != threads || c.rb_cap != occ_cap) {
+        if (lds > 65536) MBRWT_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int dev_cus = 0, per_cu = 0;
+        (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c.device);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds) != hipSuccess || per_cu <= 0)
+            per_cu = 1;
+        if (occ_cap) per_cu = std::min(per_cu, occ_cap);
+        c.rb_fn = fn;
+        c.rb_lds = lds;
+        c.rb_threads = threads;
+        c.rb_cap = occ_cap;
+        c.rb_blocks = std::max(1, dev_cus) * per_cu;
+    }
+    *blocks = (uint64_t)c.rb_blocks;
+    return MBRWT_OK;
+}
+
+int timing_events(Ctx &c, bool async, hipEvent_t *e0, hipEvent_t *e1) {
+    *e0 = c.ev0;
+    *e1 = c.ev1;
+    if (!c.timing || !async) return MBRWT_OK;
+    if (c.async_ev.size() <= c.async_used) {
+        hipEvent_t ea = nullptr, eb = nullptr;
+        MBRWT_HIP(hipEventCreate(&ea));
+        MBRWT_HIP(hipEventCreate(&eb));
+        c.async_ev.push_back({ea, eb});
+    }
+    *e0 = c.async_ev[c.async_used].first;
+    *e1 = c.async_ev[c.async_used].second;
+    ++c.async_used;
+    return MBRWT_OK;
+}
+
+// a synchronous call's status block on the host (`words` of d_scalars), and
+// its kernel time between ev0 and ev1 into the context's timing
+static int sync_status(Ctx &c, size_t words, hipStream_t s) {
+    MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    MBRWT_HIP(hipStreamSynchronize(s));
+    if (c.timing) {
+        float ms = 0;
+        MBRWT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+        c.timing_ms += ms;
+        c.timing_launches += 1;
+    }
+    return MBRWT_OK;
+}
+
+int finish_rows_call(Ctx &c, uint64_t *needed, const char *fallback, hipStream_t s) {
+    if (const int rc = sync_status(c, 2, s)) return rc;
+    if (needed) *needed = c.h_scalars[0];
+    switch (c.h_scalars[1]) {
+        case MBRWT_OK: return MBRWT_OK;
+        case MBRWT_ERR_RANGE: set_error("row out of range"); return MBRWT_ERR_RANGE;
+        case MBRWT_ERR_CAPACITY: set_error("cols_cap too small"); return MBRWT_ERR_CAPACITY;
+        default: set_error(fallback); return MBRWT_ERR_DEVICE;
     }
 }
 
-// the default p2w kernel stores u16 temp labels (label indices < num_columns)
-static bool p2w_label16(const Ctx &c) { return c.kernel_variant == 0 && c.tree.num_columns <= 0x10000u; }
+int node_error_code(uint64_t bits, const char **msg) {
+    if (bits & 1) {
+        if (msg) *msg = "row out of range";
+        return MBRWT_ERR_RANGE;
+    }
+    if (bits & 2) {
+        if (msg) *msg = "traversal stack overflow";
+        return MBRWT_ERR_UNSUPPORTED;
+    }
+    return MBRWT_OK;
+}
 
-static uint32_t p2w_ring(const Ctx &c) {
-    (void)c;
-    return 512;
+int finish_nodes_call(Ctx &c, uint64_t cap, uint64_t *needed, uint64_t *overflow, hipStream_t s) {
+    if (const int rc = sync_status(c, 4, s)) return rc;
+    const char *msg = nullptr;
+    if (const int rc = node_error_code(c.h_scalars[2], &msg)) {
+        set_error(msg);
+        return rc;
+    }
+    const uint64_t total = c.h_scalars[0];
+    *overflow = c.h_scalars[1];
+    if (needed) *needed = total;
+    if (total > cap) {
+        set_error("cols_cap too small");
+        return MBRWT_ERR_CAPACITY;
+    }
+    return MBRWT_OK;
+}
+
+using P2wFn = void (*)(P2wParams);
+
+// labels of a wave's LDS ring in k_traverse_p2w (profiles/r02/v32_p2w_c4_sweep.log)
+constexpr uint32_t kP2wRing = 512;
+constexpr uint32_t kP2wWpb = 4;  // waves per workgroup (its __launch_bounds__)
+
+// the p2w kernel stores u16 temp labels when they fit (label indices < num_columns)
+static bool p2w_label16(const Ctx &c) { return c.tree.num_columns <= 0x10000u; }
+
+// k_traverse_p2w for this context?  Default for trees with a P2W table
+// (non-temporal block reads on images larger than 1 GiB).
+static P2wFn p2w_kernel(const Ctx &c) {
+    if (c.tree.p2w_table.empty() || !c.d_p2w || c.kernel_variant != 0) return nullptr;
+    const bool big = c.tree.image_bytes > (1ull << 30);
+    if (p2w_label16(c)) return big ? k_traverse_p2w<true, uint16_t> : k_traverse_p2w<false, uint16_t>;
+    return big ? k_traverse_p2w<true> : k_traverse_p2w<false>;
 }
 
 static size_t p2w_lds_bytes(const Ctx &c) {
-    return ((c.tree.p2w_table.size() + 3) & ~size_t(3)) * 4 + 4 * (size_t)(kP2wWaveWords + p2w_ring(c)) * 4;
+    return ((c.tree.p2w_table.size() + 3) & ~size_t(3)) * 4 + kP2wWpb * (size_t)(kP2wWaveWords + kP2wRing) * 4;
 }
 
 // k_traverse_ptw for this context?  Default for trees with a PTW table
-// (MBRWT_OPT_KERNEL 0 or 24..30): 24 plain reads, 25 non-temporal, 26/27 the
-// same with 8 waves per workgroup, 28/29 with 16 (512-label rings: LDS holds
-// 16 waves per CU); 30 and the default: 7 waves per workgroup with a
-// 256-label ring (21 waves per CU; 2.27 vs 2.47 ms at the greedy + relax shape).
-struct PtwPick {
-    P2wFn fn = nullptr;
-    uint32_t wpb = 4;
-    uint32_t ring = 512;
-    bool wide = false;
-    bool label16 = false;  // u16 temp labels (the default 7-wave kernel; PTW columns are < 2^15)
-};
-template <bool NT, bool WIDE, int MAXD>
-static P2wFn ptw_fn(uint32_t wpb) {
-    (void)wpb;  // (the default 7-wave kernel only; the r02 wave-count variants were retired)
-    return k_traverse_ptw<NT, WIDE, MAXD, 7, 256, uint16_t>;
-}
-static PtwPick ptw_kernel(const Ctx &c) {
-    PtwPick r;
-    const int kv = c.kernel_variant;
+// (non-temporal block reads on images larger than 1 GiB).
+static bool ptw_wide(const Ctx &c) { return c.tree.ptw_table[0] > 8; }  // a second 64-byte half of root children
+static P2wFn ptw_kernel(const Ctx &c) {
     const auto &t = c.tree.ptw_table;
-    if (t.empty() || !c.d_ptw || !(kv == 0 || (kv >= 24 && kv <= 30))) return r;
-    const bool nt = kv == 0 || kv == 30 ? c.tree.image_bytes > (1ull << 30) : (kv & 1) != 0;
-    r.wpb = (kv == 0 || kv == 30) ? 7 : kv >= 28 ? 16 : kv >= 26 ? 8 : 4;  // default: 7 waves, 256-label ring
-    r.ring = r.wpb == 7 ? 256 : 512;
-    r.label16 = r.wpb == 7;
-    r.wide = t[0] > 8;
-    const bool deep = t[3] > 4;
-#define PTW(NTV, W, D) if (nt == NTV && r.wide == W && deep == D) r.fn = ptw_fn<NTV, W, D ? 8 : 4>(r.wpb);
+    if (t.empty() || !c.d_ptw || c.kernel_variant != 0) return nullptr;
+    const bool nt = c.tree.image_bytes > (1ull << 30), wide = ptw_wide(c), deep = t[3] > 4;
+#define PTW(NTV, W, D) if (nt == NTV && wide == W && deep == D) return k_traverse_ptw<NTV, W, D ? 8 : 4>;
     PTW(false, false, false) PTW(false, false, true) PTW(false, true, false) PTW(false, true, true)
     PTW(true, false, false) PTW(true, false, true) PTW(true, true, false) PTW(true, true, true)
 #undef PTW
-    return r;
+    return nullptr;
+}
+
+static size_t ptw_lds_bytes(const Ctx &c) {
+    const size_t per_wave = ptw_wide(c) ? PtwLayout<true>::kWords : PtwLayout<false>::kWords;
+    return ((c.tree.ptw_table.size() + 3) & ~size_t(3)) * 4 + kPtwWpb * per_wave * 4;
 }
 
 const char *traverse_kernel_name(const Ctx &c) {
     if (c.rows.ready && c.kernel_variant == 0) return c.rows.var ? "k_var_decode" : "k_traverse_rows";
     if (c.nodes_freed) return "";
-    if (ptw_kernel(c).fn) return "k_traverse_ptw";
+    if (ptw_kernel(c)) return "k_traverse_ptw";
     if (p2w_kernel(c)) return "k_traverse_p2w";
     const Trav t = pick_traverse<MODE_SLOTS>(c);
     return t ? t.name : "";
@@ -2117,7 +2181,7 @@ const char *traverse_kernel_name(const Ctx &c) {
 // get_rows through k_traverse_p2w: rowblocks of 16 rows, each written to its
 // own temp region of C = 16 K labels; one scan over the rowblock totals; the
 // compaction; the direct pass for overflowing rowblocks.
-// (k_traverse_ptw: the same driver over the PTW table, `wpb` waves per workgroup)
+// (k_traverse_ptw: the same driver over the PTW table)
 struct RowblockKernel {
     P2wFn fn;
     const uint32_t *table;
@@ -2162,7 +2226,7 @@ static int run_get_rows_p2w(Ctx &c, const RowblockKernel &kr, const uint64_t *d_
     p.table_words = kr.table_words;
     p.table = kr.table;
     p.C = C;
-    p.S = p2w_ring(c);
+    p.S = kP2wRing;  // (k_traverse_ptw: its ring is a compile-time constant)
     p.temp = reinterpret_cast<uint32_t *>(c.ws_temp.buf);
     p.counts = d_counts;
     p.block_counts = d_block_counts;
@@ -2171,22 +2235,9 @@ static int run_get_rows_p2w(Ctx &c, const RowblockKernel &kr, const uint64_t *d_
 
     const size_t lds = kr.lds;
     const uint32_t threads = 64 * kr.wpb;
-    if (c.rb_fn != reinterpret_cast<const void *>(kfn) || c.rb_lds != lds || c.rb_threads != threads) {
-        if (lds > 65536)
-            MBRWT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int dev_cus = 0, per_cu = 0;
-        (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c.device);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kfn), threads, lds) !=
-                hipSuccess ||
-            per_cu <= 0)
-            per_cu = 1;
-        c.rb_fn = reinterpret_cast<const void *>(kfn);
-        c.rb_lds = lds;
-        c.rb_threads = threads;
-        c.rb_blocks = std::max(1, dev_cus) * per_cu;
-    }
-    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((nb + kr.wpb - 1) / kr.wpb, (uint64_t)c.rb_blocks));
+    uint64_t resident = 0;
+    if ((rc = resident_workgroups(c, reinterpret_cast<const void *>(kfn), threads, lds, 0, &resident))) return rc;
+    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((nb + kr.wpb - 1) / kr.wpb, resident));
 
     MBRWT_HIP(hipMemsetAsync(c.d_scalars, 0, 8 * sizeof(uint64_t), s));
     MBRWT_HIP(hipMemsetAsync(d_block_counts + nb, 0, sizeof(uint32_t), s));
@@ -2215,28 +2266,8 @@ static int run_get_rows_p2w(Ctx &c, const RowblockKernel &kr, const uint64_t *d_
                            lm, map_lds, cap);
     MBRWT_HIP(hipGetLastError());
     MBRWT_HIP(hipMemcpyAsync(c.d_scalars, d_block_offsets + nb, sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-    MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    MBRWT_HIP(hipStreamSynchronize(s));
-    if (c.timing) {
-        float ms = 0;
-        MBRWT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-        c.timing_ms += ms;
-        c.timing_launches += 1;
-    }
-    const uint64_t total = c.h_scalars[0], ovf = c.h_scalars[1], err = c.h_scalars[2];
-    if (err & 1) {
-        set_error("row out of range");
-        return MBRWT_ERR_RANGE;
-    }
-    if (err & 2) {
-        set_error("traversal stack overflow");
-        return MBRWT_ERR_UNSUPPORTED;
-    }
-    if (needed) *needed = total;
-    if (total > cap) {
-        set_error("cols_cap too small");
-        return MBRWT_ERR_CAPACITY;
-    }
+    uint64_t ovf = 0;
+    if ((rc = finish_nodes_call(c, cap, needed, &ovf, s))) return rc;
     if (ovf) {
         TravParams q = base_params(c);
         q.rows = d_rows;
@@ -2273,16 +2304,13 @@ int run_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets
         set_error("batch larger than 2^31 rows");
         return MBRWT_ERR_UNSUPPORTED;
     }
-    if (const PtwPick pk = ptw_kernel(c); pk.fn) {
-        const size_t words = c.tree.ptw_table.size();
-        const size_t per_wave = pk.ring == 256 ? (pk.wide ? PtwLayout<true, 256>::kWords : PtwLayout<false, 256>::kWords)
-                                               : (pk.wide ? PtwLayout<true>::kWords : PtwLayout<false>::kWords);
-        const RowblockKernel kr{pk.fn, c.d_ptw, (uint32_t)words, ((words + 3) & ~size_t(3)) * 4 + pk.wpb * per_wave * 4,
-                                pk.wpb, true, pk.label16};
+    if (const P2wFn kfn = ptw_kernel(c)) {
+        const RowblockKernel kr{kfn, c.d_ptw, (uint32_t)c.tree.ptw_table.size(), ptw_lds_bytes(c), kPtwWpb, true,
+                                sizeof(PtwLabel) == 2};
         return run_get_rows_p2w(c, kr, d_rows, n, d_offsets, d_cols, cap, needed, s);
     }
     if (const P2wFn kfn = p2w_kernel(c)) {
-        const RowblockKernel kr{kfn, c.d_p2w, (uint32_t)c.tree.p2w_table.size(), p2w_lds_bytes(c), 4, false,
+        const RowblockKernel kr{kfn, c.d_p2w, (uint32_t)c.tree.p2w_table.size(), p2w_lds_bytes(c), kP2wWpb, false,
                                 p2w_label16(c)};
         return run_get_rows_p2w(c, kr, d_rows, n, d_offsets, d_cols, cap, needed, s);
     }
@@ -2328,28 +2356,8 @@ int run_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets
     if (c.timing) MBRWT_HIP(hipEventRecord(c.ev1, s));
     MBRWT_HIP(hipcub::DeviceScan::ExclusiveSum(c.ws_scan.buf, scan_bytes, it, scan_out, scan_n, s));
     MBRWT_HIP(hipMemcpyAsync(c.d_scalars, scan_out + scan_n - 1, sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-    MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    MBRWT_HIP(hipStreamSynchronize(s));
-    if (c.timing) {
-        float ms = 0;
-        MBRWT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-        c.timing_ms += ms;
-        c.timing_launches += 1;
-    }
-    const uint64_t total = c.h_scalars[0], ovf = c.h_scalars[1], err = c.h_scalars[2];
-    if (err & 1) {
-        set_error("row out of range");
-        return MBRWT_ERR_RANGE;
-    }
-    if (err & 2) {
-        set_error("traversal stack overflow");
-        return MBRWT_ERR_UNSUPPORTED;
-    }
-    if (needed) *needed = total;
-    if (total > cap) {
-        set_error("cols_cap too small");
-        return MBRWT_ERR_CAPACITY;
-    }
+    uint64_t ovf = 0;
+    if ((rc = finish_nodes_call(c, cap, needed, &ovf, s))) return rc;
     {
         const uint32_t map_lds = label_map_lds(c);
         if (fn.fast) {  // chunk-packed output (k_traverse_fast2)
@@ -2387,8 +2395,7 @@ int run_count_work(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *visits,
     if (n) MBRWT_HIP(launch(c, fn, n, s, p));
     MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     MBRWT_HIP(hipStreamSynchronize(s));
-    if (c.h_scalars[2] & 1) return MBRWT_ERR_RANGE;
-    if (c.h_scalars[2] & 2) return MBRWT_ERR_UNSUPPORTED;
+    if (const int rc = node_error_code(c.h_scalars[2])) return rc;
     if (visits) *visits = c.h_scalars[3];
     if (labels) *labels = c.h_scalars[4];
     return MBRWT_OK;
@@ -2409,9 +2416,7 @@ int run_count_labels(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_cou
     if (n) MBRWT_HIP(launch(c, fn, n, s, p));
     MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     MBRWT_HIP(hipStreamSynchronize(s));
-    if (c.h_scalars[2] & 1) return MBRWT_ERR_RANGE;
-    if (c.h_scalars[2] & 2) return MBRWT_ERR_UNSUPPORTED;
-    return MBRWT_OK;
+    return node_error_code(c.h_scalars[2]);
 }
 
 int run_get_batch(Ctx &c, const uint64_t *d_rows, const uint64_t *d_cols, uint64_t n, uint8_t *d_out, hipStream_t s) {
@@ -2427,8 +2432,7 @@ int run_get_batch(Ctx &c, const uint64_t *d_rows, const uint64_t *d_cols, uint64
     MBRWT_HIP(hipGetLastError());
     MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     MBRWT_HIP(hipStreamSynchronize(s));
-    if (c.h_scalars[2] & 1) return MBRWT_ERR_RANGE;
-    return MBRWT_OK;
+    return node_error_code(c.h_scalars[2]);  // (k_get raises the range bit only)
 }
 
 }  // namespace mbrwt

@@ -2276,38 +2276,12 @@ int rows_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offset
     // 0.456 at 4, C2 0.068 against 0.073: profiles/r03/v06_rows_occupancy_*);
     // MBRWT_BUILD_ROWS_WGS_PER_CU (when the image is built) overrides
     const int occ_cap = im.occ_cap ? (int)im.occ_cap : (int)std::max(1u, 24u / wpb);
-    if (c.rb_fn != reinterpret_cast<const void *>(kfn) || c.rb_lds != lds || c.rb_threads != threads ||
-        c.rb_cap != occ_cap) {
-        if (lds > 65536)
-            MBRWT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int dev_cus = 0, per_cu = 0;
-        (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c.device);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kfn), threads, lds) !=
-                hipSuccess ||
-            per_cu <= 0)
-            per_cu = 1;
-        per_cu = std::min(per_cu, occ_cap);
-        c.rb_cap = occ_cap;
-        c.rb_fn = reinterpret_cast<const void *>(kfn);
-        c.rb_lds = lds;
-        c.rb_threads = threads;
-        c.rb_blocks = std::max(1, dev_cus) * per_cu;
-    }
+    uint64_t resident = 0;
+    if ((rc = resident_workgroups(c, reinterpret_cast<const void *>(kfn), threads, lds, occ_cap, &resident))) return rc;
 
     c.rows_sc_dirty = true;  // until k_compact_tiles has run
-    hipEvent_t e0 = c.ev0, e1 = c.ev1;
-    if (c.timing && d_status) {  // asynchronous calls: one event pair per call, summed by mbrwt_take_timing
-        if (c.async_ev.size() <= c.async_used) {
-            hipEvent_t ea = nullptr, eb = nullptr;
-            MBRWT_HIP(hipEventCreate(&ea));
-            MBRWT_HIP(hipEventCreate(&eb));
-            c.async_ev.push_back({ea, eb});
-        }
-        e0 = c.async_ev[c.async_used].first;
-        e1 = c.async_ev[c.async_used].second;
-        ++c.async_used;
-    }
+    hipEvent_t e0, e1;
+    if ((rc = timing_events(c, d_status != nullptr, &e0, &e1))) return rc;
     if (c.timing) MBRWT_HIP(hipEventRecord(e0, s));
     {
         // the odometer: kRowsTilesPerWave tiles per wave, the dispatcher
@@ -2318,7 +2292,7 @@ int rows_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offset
         const bool persistent = walk != WALK_ODOMETER && !im.term;  // (terminal records: a small table)
         const uint64_t per_wg = (uint64_t)wpb * kRowsTilesPerWave;
         const uint64_t g = persistent
-                               ? std::max<uint64_t>(1, std::min<uint64_t>((nt + wpb - 1) / wpb, (uint64_t)c.rb_blocks))
+                               ? std::max<uint64_t>(1, std::min<uint64_t>((nt + wpb - 1) / wpb, resident))
                                : std::max<uint64_t>(1, std::min<uint64_t>((nt + per_wg - 1) / per_wg, 1ull << 30));
         hipLaunchKernelGGL(kfn, dim3((unsigned)g), dim3(threads), lds, s, p);
         MBRWT_HIP(hipGetLastError());
@@ -2364,22 +2338,7 @@ int rows_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offset
         c.rows_sc_dirty = false;
     }
     if (d_status) return MBRWT_OK;  // no host synchronisation: the status lands on the stream
-    MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    MBRWT_HIP(hipStreamSynchronize(s));
-    if (c.timing) {
-        float ms = 0;
-        MBRWT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-        c.timing_ms += ms;
-        c.timing_launches += 1;
-    }
-    const uint64_t total = c.h_scalars[0], st = c.h_scalars[1];
-    if (needed) *needed = total;
-    switch (st) {
-        case MBRWT_OK: return MBRWT_OK;
-        case MBRWT_ERR_RANGE: set_error("row out of range"); return MBRWT_ERR_RANGE;
-        case MBRWT_ERR_CAPACITY: set_error("cols_cap too small"); return MBRWT_ERR_CAPACITY;
-        default: set_error("row-record walk failed (corrupt image)"); return MBRWT_ERR_DEVICE;
-    }
+    return finish_rows_call(c, needed, "row-record walk failed (corrupt image)", s);
 }
 
 namespace {

@@ -832,36 +832,12 @@ int var_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets
     const VarFn kfn = var_fn(G);
     const size_t lds = ((p.U + 32) * 2 + 15) / 16 * 16 + kVarWpb * (size_t)(CR + CR / 16 + 2 * CS);
     const uint32_t threads = 64 * kVarWpb;
-    if (c.rb_fn != reinterpret_cast<const void *>(kfn) || c.rb_lds != lds || c.rb_threads != threads) {
-        if (lds > 65536)
-            MBRWT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int dev_cus = 0, per_cu = 0;
-        (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c.device);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kfn), threads, lds) !=
-                hipSuccess ||
-            per_cu <= 0)
-            per_cu = 1;
-        if (im.occ_cap) per_cu = std::min<int>(per_cu, (int)im.occ_cap);
-        c.rb_fn = reinterpret_cast<const void *>(kfn);
-        c.rb_lds = lds;
-        c.rb_threads = threads;
-        c.rb_cap = 0;
-        c.rb_blocks = std::max(1, dev_cus) * per_cu;
-    }
+    uint64_t resident = 0;  // (capped only by MBRWT_BUILD_ROWS_WGS_PER_CU)
+    if ((rc = resident_workgroups(c, reinterpret_cast<const void *>(kfn), threads, lds, (int)im.occ_cap, &resident)))
+        return rc;
     c.rows_sc_dirty = true;  // until k_var_decode has run
-    hipEvent_t e0 = c.ev0, e1 = c.ev1;
-    if (c.timing && d_status) {
-        if (c.async_ev.size() <= c.async_used) {
-            hipEvent_t ea = nullptr, eb = nullptr;
-            MBRWT_HIP(hipEventCreate(&ea));
-            MBRWT_HIP(hipEventCreate(&eb));
-            c.async_ev.push_back({ea, eb});
-        }
-        e0 = c.async_ev[c.async_used].first;
-        e1 = c.async_ev[c.async_used].second;
-        ++c.async_used;
-    }
+    hipEvent_t e0, e1;
+    if ((rc = timing_events(c, d_status != nullptr, &e0, &e1))) return rc;
     hipLaunchKernelGGL(k_var_locate, dim3((unsigned)simple_grid(n + 1)), dim3(256), 0, s, p);
     MBRWT_HIP(hipGetLastError());
     MBRWT_HIP(hipcub::DeviceScan::ExclusiveSum(c.ws_scan.buf, sb, it, d_offsets, n + 1, s));
@@ -870,29 +846,14 @@ int var_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets
         const uint64_t R = 64 / G, nt = (n + R - 1) / R;
         // (persistent: one tile per wave, as k_traverse_rows, measured 1.4 %
         // slower here -- 2.215 vs 2.185 ms per 10 M rows at C3, profiles/r05)
-        const uint64_t g = std::max<uint64_t>(1, std::min<uint64_t>((nt + kVarWpb - 1) / kVarWpb, (uint64_t)c.rb_blocks));
+        const uint64_t g = std::max<uint64_t>(1, std::min<uint64_t>((nt + kVarWpb - 1) / kVarWpb, resident));
         hipLaunchKernelGGL(kfn, dim3((unsigned)g), dim3(threads), lds, s, p);
         MBRWT_HIP(hipGetLastError());
     }
     if (c.timing) MBRWT_HIP(hipEventRecord(e1, s));
     c.rows_sc_dirty = false;
     if (d_status) return MBRWT_OK;
-    MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    MBRWT_HIP(hipStreamSynchronize(s));
-    if (c.timing) {
-        float ms = 0;
-        MBRWT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-        c.timing_ms += ms;
-        c.timing_launches += 1;
-    }
-    const uint64_t total = c.h_scalars[0], st = c.h_scalars[1];
-    if (needed) *needed = total;
-    switch (st) {
-        case MBRWT_OK: return MBRWT_OK;
-        case MBRWT_ERR_RANGE: set_error("row out of range"); return MBRWT_ERR_RANGE;
-        case MBRWT_ERR_CAPACITY: set_error("cols_cap too small"); return MBRWT_ERR_CAPACITY;
-        default: set_error("variable-length record decode failed"); return MBRWT_ERR_DEVICE;
-    }
+    return finish_rows_call(c, needed, "variable-length record decode failed", s);
 }
 
 int var_get_batch(Ctx &c, const uint64_t *d_rows, const uint64_t *d_cols, uint64_t n, uint8_t *d_out, hipStream_t s) {

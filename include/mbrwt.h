@@ -537,13 +537,13 @@ int mbrwt_unpack_offsets_device(const void *d_base, uint32_t nseg, uint64_t seg_
 
 #define MBRWT_OPT_TIMING 1       /* 1: time the traversal kernel with HIP events */
 #define MBRWT_OPT_SLOT_LABELS 2  /* per-row label slots of the fast path (0 = auto) */
-#define MBRWT_OPT_KERNEL 4       /* traversal kernel (A/B measurement): 0 default (k_traverse_p2w, else
-                                    k_traverse_fast2 where eligible, else the group kernel), 1 lane-per-row,
-                                    2/3/4 group with 1/2/4 children per lane, 5/6 group at 8/6 waves per
-                                    SIMD, 10 group + non-temporal reads, 17/18 k_traverse_fast2 plain /
-                                    non-temporal, 19/20 k_traverse_p2w plain / non-temporal, 24..30
-                                    k_traverse_ptw configurations (each falls back to the next kernel where
-                                    the tree is not eligible); others rejected.  Node images only. */
+#define MBRWT_OPT_KERNEL 4       /* traversal kernel: 0 the default (the row-record kernels; on node images
+                                    k_traverse_ptw / k_traverse_p2w / k_traverse_fast2 where the tree is
+                                    eligible, else the group kernel), 1 the lane-per-row node-image kernel
+                                    (A/B and tests; needs layout NODES or BOTH, else MBRWT_ERR_UNSUPPORTED).
+                                    The retired A/B variants 2..6, 10, 17..20 and 24..30 return
+                                    MBRWT_ERR_UNSUPPORTED (what they measured: profiles/r02 .. r04), any
+                                    other value MBRWT_ERR_INVALID. */
 #define MBRWT_OPT_ROWS_WALK 8  /* row records: 0 default (the odometer walk over the path table on uniform
                                    trees, the tree odometer on every other shape of <= 8 internal levels),
                                    3 the tree odometer, 4 the stack walk, 6 the stack walk of one-byte masks,

@@ -88,7 +88,9 @@ def main():
     ap.add_argument("--relax", type=int, default=10)
     ap.add_argument("--batch", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--variants", default="0,5")
+    ap.add_argument("--variants", default="0",
+                    help="comma-separated MBRWT_OPT_KERNEL values (0 the default, 1 the lane-per-row node kernel) "
+                         "and, on row records, wN = MBRWT_OPT_ROWS_WALK N")
     ap.add_argument("--scaled-rows", type=int, default=0,
                     help="also measure the greedy + relax SHAPE of the C2 build with the synthetic law at this "
                          "many rows (mbrwt_create_synthetic_shaped; parity by the streamed shaped oracle)")
@@ -116,6 +118,16 @@ def main():
     from genome_graph_annotation_amd import BRWTDevice
 
     variants = [x if x.startswith("w") else int(x) for x in a.variants.split(",")]
+    # a value the library rejects (the retired r02-r04 variants) fails here,
+    # with the library's message, before any tree is built or timed
+    from genome_graph_annotation_amd import _lib as L
+    probe = BRWTDevice.synthetic(1000, 16, 0.1, 2, 42, layout=a.layout)
+    for v in variants:
+        if isinstance(v, str):
+            probe.set_option(L.MBRWT_OPT_ROWS_WALK, int(v[1:]))
+        else:
+            probe.set_option(L.MBRWT_OPT_KERNEL, v)
+    del probe
     rows_np = np.random.default_rng(42).integers(0, a.rows, a.batch, dtype=np.uint64)
     res = {}
     shapes = {}

@@ -1,6 +1,7 @@
-"""A/B sweep of traversal-kernel variants on one structure, in one process
-(interleaved repetitions, HIP-event kernel times).  Calibration tool, not the
-bench: python tools/sweep.py --rows 3700000000 --batch 8000000"""
+"""A/B sweep of the node-image traversal kernels (MBRWT_OPT_KERNEL 0: the
+default family of the tree, 1: the lane-per-row kernel) on one structure, in
+one process (interleaved repetitions, HIP-event kernel times).  Calibration
+tool, not the bench: python tools/sweep.py --rows 3700000000 --batch 8000000"""
 import argparse
 import os
 import sys
@@ -20,17 +21,23 @@ ap.add_argument("--density", type=float, default=0.003)
 ap.add_argument("--arity", type=int, default=8)
 ap.add_argument("--batch", type=int, default=8_000_000)
 ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--variants", default="1,2,3,4")
+ap.add_argument("--variants", default="0,1", help="MBRWT_OPT_KERNEL values (include/mbrwt.h)")
 ap.add_argument("--presort", action="store_true", help="sort the batch on the host (locality experiment)")
 ap.add_argument("--fold", default="1", help="root folding settings to build, e.g. 0,1")
 a = ap.parse_args()
-ap2 = a
+variants = [int(x) for x in a.variants.split(",")]
+# a value the library rejects (the retired r02-r04 variants) fails here, with
+# the library's message, before anything large is built or timed
+probe = BRWTDevice.synthetic(1000, 16, 0.1, 2, 42, layout="nodes")
+for var in variants:
+    probe.set_option(L.MBRWT_OPT_KERNEL, var)
+del probe
 mats = {}
 for fold in a.fold.split(","):
     t0 = time.time()
     kinds = L.MBRWT_KIND_ALL if fold != "0" else L.MBRWT_KIND_ALL & ~L.MBRWT_KIND_FOLD_ROOT
     with build_option(L.MBRWT_BUILD_NODE_KINDS, kinds):
-        mats[fold] = BRWTDevice.synthetic(a.rows, a.cols, a.density, a.arity, 42)
+        mats[fold] = BRWTDevice.synthetic(a.rows, a.cols, a.density, a.arity, 42, layout="nodes")
     print(f"built fold={fold} {mats[fold].device_bytes() / 1e9:.1f} GB in {time.time() - t0:.1f}s", flush=True)
 m = next(iter(mats.values()))
 rows_np = np.random.default_rng(42).integers(0, a.rows, a.batch, dtype=np.uint64)
@@ -42,7 +49,6 @@ s = torch.cuda.current_stream().cuda_stream
 v, lab = m.count_work_device(rows, s)
 cols = torch.empty(2 * lab + 1024, dtype=torch.int32, device="cuda")  # diagnostic variants may emit more
 alg = 64 * v + 16 * a.batch + 4 * lab
-variants = [int(x) for x in a.variants.split(",")]
 sorts = [0]
 res = {}
 ref = None  # every variant's CSR must equal the first one's (bit-exact)
