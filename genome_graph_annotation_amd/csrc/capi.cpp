@@ -271,22 +271,20 @@ static int make_rows(Ctx &c, int layout) {
         return MBRWT_ERR_UNSUPPORTED;
     }
     const bool sharded = !c.shards.empty();
-    RowsBuild *rb = rows_build_begin(c, c.tree.num_rows, sharded ? c.shard_rows : kRowsAlign, layout == LAYOUT_AUTO);
-    if (!rb) return MBRWT_ERR_NOMEM;
     int rc = MBRWT_OK;
-    if (!sharded) {
-        rc = rows_build_range(rb, c, 0);
-    } else {
-        for (size_t k = 0; k < c.shards.size() && !rc; ++k) {
-            rc = rows_build_range(rb, *c.shards[k], (uint64_t)k * c.shard_rows);
-            if (!rc) (void)hipSetDevice(c.device);
+    {
+        RowsBuildPtr rb(rows_build_begin(c, c.tree.num_rows, sharded ? c.shard_rows : kRowsAlign, layout == LAYOUT_AUTO));
+        if (!rb) return MBRWT_ERR_NOMEM;
+        if (!sharded) {
+            rc = rows_build_range(rb.get(), c, 0);
+        } else {
+            for (size_t k = 0; k < c.shards.size() && !rc; ++k) {
+                rc = rows_build_range(rb.get(), *c.shards[k], (uint64_t)k * c.shard_rows);
+                if (!rc) (void)hipSetDevice(c.device);
+            }
         }
-    }
-    if (!rc) {
-        rc = rows_build_finish(rb);
-    } else {
-        rows_build_abort(rb);
-    }
+        if (!rc) rc = rows_build_finish(rb.release());
+    }  // (a build that failed in a range is freed here, before the fallback)
     if (rc && layout == LAYOUT_AUTO && (rc == MBRWT_ERR_UNSUPPORTED || rc == MBRWT_ERR_NOMEM)) {
         (void)hipGetLastError();
         return MBRWT_OK;  // outside the row-record limits or too large: the per-node images answer
@@ -314,13 +312,13 @@ static int create_rows_ranged(int device, uint64_t num_rows, uint64_t num_column
             c.tree.num_columns = num_columns;
             const bool fixed = build_tuning().rows_range != 0;
             uint64_t R = fixed ? rows_range_rows() : std::min(rows_range_rows(), kRowsFirstRange);
-            RowsBuild *rb = rows_build_begin(c, num_rows, kRowsAlign, layout == LAYOUT_AUTO);
+            RowsBuildPtr rb(rows_build_begin(c, num_rows, kRowsAlign, layout == LAYOUT_AUTO));
             if (!rb) return (int)MBRWT_ERR_NOMEM;
             for (uint64_t a = 0, b = 0; a < num_rows; a = b) {
                 b = std::min(num_rows, a + R);
                 mbrwt_ctx *sub = nullptr;
                 int rc = create_common(device, &sub, [&](Ctx &sc) { return build_range(sc, a, b); }, kNoLayoutHook);
-                if (!rc) rc = rows_build_range(rb, *C(sub), a);
+                if (!rc) rc = rows_build_range(rb.get(), *C(sub), a);
                 if (!rc && !fixed && a == 0 && b < num_rows) {
                     // later ranges: what the first range's node image costs per
                     // row, into the memory its release leaves free less the
@@ -330,7 +328,7 @@ static int create_rows_ranged(int device, uint64_t num_rows, uint64_t num_column
                     size_t free_b = 0, total_b = 0;
                     (void)hipMemGetInfo(&free_b, &total_b);
                     const double avail = (double)free_b + (double)C(sub)->tree.image_bytes - 8.0 * (1ull << 30) -
-                                         (double)rows_build_pending_bytes(rb, num_rows - b);
+                                         (double)rows_build_pending_bytes(rb.get(), num_rows - b);
                     const double fit = per_row > 0 ? avail / (1.2 * per_row) : (double)rows_range_rows();
                     R = std::max<uint64_t>(kRowsAlign, std::min<uint64_t>(rows_range_rows(),
                                                                           (uint64_t)std::max(0.0, fit) / kRowsAlign *
@@ -349,12 +347,9 @@ static int create_rows_ranged(int device, uint64_t num_rows, uint64_t num_column
                 }
                 if (sub) release(C(sub));
                 (void)hipSetDevice(device);
-                if (rc) {
-                    rows_build_abort(rb);
-                    return rc;
-                }
+                if (rc) return rc;  // (rb frees the build)
             }
-            const int rc = rows_build_finish(rb);
+            const int rc = rows_build_finish(rb.release());
             if (rc) return rc;
             for (DevNode &d : c.tree.nodes) d.base = 0;
             c.nodes_freed = true;

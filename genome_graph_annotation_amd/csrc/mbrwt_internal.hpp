@@ -26,8 +26,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <functional>
@@ -436,14 +438,25 @@ struct Ctx {
 // range.num_rows) written from the node image of `range` (a context over
 // those rows, tables uploaded); the first range measured decides the block
 // size and rows per block (S must divide `align`: every later range starts at
-// a multiple of it).  finish_rows uploads the table and marks the image ready.
+// a multiple of it).  rows_build_finish uploads the tables, moves the image
+// into `top` and frees the build, also when it fails; rows_build_abort frees a
+// build that is not finished (RowsBuildPtr: the scoped owner of one).
 struct RowsBuild;
 RowsBuild *rows_build_begin(Ctx &top, uint64_t num_rows, uint64_t align, bool auto_layout = false);
 int rows_build_range(RowsBuild *rb, Ctx &range, uint64_t row0);
-int rows_build_finish(RowsBuild *rb);  // frees rb
+int rows_build_finish(RowsBuild *rb);  // frees rb: rows_build_finish(owner.release())
 uint64_t rows_build_pending_bytes(const RowsBuild *rb, uint64_t rows);
 void rows_build_abort(RowsBuild *rb);
+struct RowsBuildAbort {
+    void operator()(RowsBuild *rb) const { rows_build_abort(rb); }
+};
+using RowsBuildPtr = std::unique_ptr<RowsBuild, RowsBuildAbort>;
 void free_rows(RowsImage &r);
+// launch grid of a grid-stride kernel over `items`: workgroups of 256
+// threads, one thread per item up to 65536 workgroups
+inline unsigned grid256(uint64_t items) {
+    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, 65536));
+}
 // row-record queries (rows.hip)
 // d_status != null: asynchronous (no host synchronisation; the call's
 // {labels needed, status, sticky status bits} land in d_status on the stream)

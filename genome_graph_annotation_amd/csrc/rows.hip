@@ -14,11 +14,16 @@
 // resolved once, when the image is built from a node image (any of its
 // layouts), not per query.
 //
-// Build (rows_build_*): per range of rows, one thread per row walks the node
-// image and measures its record (k_rows_measure); the first range decides
-// the block size B and rows per block S from the records' sizes
-// (k_rows_plan: spilled rows and spill bytes per candidate); one thread per
-// block then writes the block and its spill entries (k_rows_write).
+// Build (rows_build_*): rows_build_range takes one range of rows through
+// named steps.  prepare_tables (once): the walk tables and the candidate
+// record code.  measure_range: one thread per row walks the node image and
+// measures its record (k_rows_measure).  On the first range, for the whole
+// image: choose_code settles the record code and choose_layout the block
+// size B and rows per block S from the records' sizes (k_rows_plan: spilled
+// rows and spill bytes per candidate) or the variable-length records, and
+// allocates the image; the rules and the cost model are pure host code in
+// rows_plan.hpp.  write_range: one thread per block writes the block and its
+// spill entries (k_rows_write).  RowsBuild's destructor is the one release.
 //
 // Query (rows_get_rows): k_traverse_rows -- one wave per tile of 64 query
 // rows: the 64 blocks are read as coalesced 16-byte quarters (one request per
@@ -36,11 +41,14 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
+#include <optional>
 
 #include "device_access.hpp"
 #include "mbrwt_internal.hpp"
 #include "pack_block.hpp"
 #include "rows_emit.hpp"
+#include "rows_plan.hpp"
 #include "rows_record.hpp"
 #include "wave_scan.hpp"
 
@@ -682,27 +690,37 @@ __global__ __launch_bounds__(256) void k_rows_write(const DevNode *nodes, uint32
     }
 }
 
-int build_grid(uint64_t items) { return (int)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, 65536)); }
-
 }  // namespace
 
 // ------------------------------------------------------------------------
 // build driver
 // ------------------------------------------------------------------------
+// The layout of the whole image, chosen on the first range (choose_layout);
+// every later range is written under it.
+struct RowsPlan {
+    bool var = false;              // variable-length records (rows_var.hip) instead of blocks
+    BlockShape block{0, 0};        // blocks: their bytes and rows per block
+    double var_bytes_per_row = 0;  // variable-length records: their size per row on the first range
+};
+
 struct RowsBuild {
     Ctx *top = nullptr;
     uint64_t n = 0, align = 1;
-    bool decided = false;
+    std::optional<RowsPlan> plan;  // unset until the first range has decided (record code: img.term / img.nib)
     bool auto_layout = false;  // layout AUTO: decline records that cost more than kAutoMaxCost requests per row
     int footprint = 0;         // MBRWT_BUILD_ROWS_FOOTPRINT of the creating thread
     VarScratch vws;            // variable-length records (rows_var.hip)
-    double var_bytes_per_row = 0;  // their size per row, measured on the first range
     RowsImage img;
     unsigned long long *d_acc = nullptr;  // [0..3] measure, [4..7] plan
     uint16_t *d_sz = nullptr;
     uint64_t sz_cap = 0;
     hipStream_t s = nullptr;
     uint32_t *d_bt = nullptr;  // terminal records: the build table (build_term_tables)
+
+    RowsBuild() = default;
+    RowsBuild(const RowsBuild &) = delete;
+    RowsBuild &operator=(const RowsBuild &) = delete;
+    ~RowsBuild();  // the one release: scratch, and the image unless rows_build_finish moved it out
 };
 
 void free_rows(RowsImage &r) {
@@ -740,15 +758,15 @@ RowsBuild *rows_build_begin(Ctx &top, uint64_t num_rows, uint64_t align, bool au
     return rb;
 }
 
-void rows_build_abort(RowsBuild *rb) {
-    if (!rb) return;
-    if (rb->d_acc) (void)hipFree(rb->d_acc);
-    if (rb->d_sz) (void)hipFree(rb->d_sz);
-    if (rb->d_bt) (void)hipFree(rb->d_bt);
-    var_free_scratch(rb->vws);
-    free_rows(rb->img);
-    delete rb;
+RowsBuild::~RowsBuild() {
+    if (d_acc) (void)hipFree(d_acc);
+    if (d_sz) (void)hipFree(d_sz);
+    if (d_bt) (void)hipFree(d_bt);
+    var_free_scratch(vws);
+    free_rows(img);
 }
+
+void rows_build_abort(RowsBuild *rb) { delete rb; }
 
 static int read_acc(RowsBuild &rb, unsigned long long *h, int k) {
     MBRWT_HIP(hipMemcpyAsync(h, rb.d_acc, k * sizeof(unsigned long long), hipMemcpyDeviceToHost, rb.s));
@@ -775,6 +793,247 @@ static int ensure_spill(RowsBuild &rb, uint64_t bytes) {
     return MBRWT_OK;
 }
 
+// the record code the image stands at: prepare_tables' candidate, settled by
+// choose_code on the first range (0 byte masks, 1 nibble codes, 2 terminal
+// records), and the terminal fields' widths (word 0 of the TT table)
+static uint32_t record_code(const RowsImage &im) { return im.term ? 2u : im.nib ? 1u : 0u; }
+static uint32_t term_width(const RowsImage &im) { return im.term ? im.table3[0] & 0xFFu : 0u; }
+static uint32_t term_id_bits(const RowsImage &im) { return im.term ? (im.table3[0] >> 8) & 0xFFu : 0u; }
+
+// Prepare, once: the RWT / RWT2 / path tables of the tree's shape and, where
+// the build options and the shape allow them, the nibble codes or the
+// terminal records' tables (TT, work table, the build table on the device).
+// Leaves the candidate record code in im.nib / im.term.
+static int prepare_tables(RowsBuild &rb, Ctx &range) {
+    RowsImage &im = rb.img;
+    if (!build_rwt_table(range.tree, im.table, im.height, im.max_arity) ||
+        !build_rwt2_table(range.tree, im.table2, im.frames, &im.slot_dnode)) {
+        im.table.clear();
+        set_error("tree shape outside the row-record limits (arity <= 64, columns < 2^16, height <= 16, a walk table of <= 8192 words)");
+        return MBRWT_ERR_UNSUPPORTED;
+    }
+    // one-byte masks everywhere (rows_walk6): the root and every internal
+    // or leaf-parent entry of arity <= 8
+    auto ar8 = [](uint32_t e) { return (e >> 30) == 2u || ((e >> 16) & 0x7Fu) <= 8; };
+    im.mask1 = ar8(im.table2[0]);
+    for (size_t i = 4; i < 4 + (size_t)im.table2[1]; ++i) im.mask1 = im.mask1 && ar8(im.table2[i]);
+    im.uni = im.mask1 ? rwt2_uniform_levels(im.table2) : 0u;
+    if (im.uni) append_path_table(im.table2, im.uni);
+    // masks wider than 16 bits (r06: arity up to 64) are read by the tree
+    // odometer and the one-lane walks only: such a tree needs the tree
+    // odometer's depth
+    // (im.max_arity: over the nodes the walk reaches -- record-only
+    // dnodes such as PACKT_IN carry other arities)
+    if (im.max_arity > 16 && im.frames > kRowsOdoLevels) {
+        im.table.clear();
+        set_error("row records: a node wider than 16 children in a tree deeper than the tree odometer (8 levels)");
+        return MBRWT_ERR_UNSUPPORTED;
+    }
+    // nibble-coded masks (MBRWT_BUILD_ROWS_CODE = 1, r06): read by the
+    // path-table odometer and the one-lane walks, so uniform trees of
+    // one-byte masks with a path table only (the others keep bytes)
+    im.nib = build_tuning().rows_code == 1 && im.uni && im.table2.size() > 3 && im.table2[3] != 0;
+    // terminal records (r06; MBRWT_BUILD_ROWS_CODE 0 = AUTO, the default,
+    // or 2): trees of masks up to 16 bits whose terminals fit the fields
+    im.term = false;
+    // (AUTO, code 0: where they are smaller than byte masks -- decided on
+    // the first range by choose_code; code 3 forces byte masks)
+    const int code = build_tuning().rows_code;
+    if ((code == 0 || code == 2) && im.max_arity <= 16) {
+        std::vector<uint32_t> bt, term_slot;
+        bool ok = build_term_tables(im.table2, im.table3, bt, term_slot);
+        if (ok) {
+            im.term_dnode.resize(term_slot.size());
+            for (size_t i = 0; i < term_slot.size(); ++i)
+                im.term_dnode[i] = term_slot[i] < im.slot_dnode.size() ? im.slot_dnode[term_slot[i]] : ~0u;
+            ok = build_work_table(range.tree, im.term_dnode, im.table4);
+        }
+        if (ok) {
+            if (!rb.d_bt) {
+                if (hipMalloc(&rb.d_bt, bt.size() * 4) != hipSuccess) return hip_fail(hipGetLastError(), "build table");
+                MBRWT_HIP(hipMemcpy(rb.d_bt, bt.data(), bt.size() * 4, hipMemcpyHostToDevice));
+            }
+            im.term = true;
+        }
+    }
+    return MBRWT_OK;
+}
+
+// k_rows_measure's counters of one range
+struct Measure {
+    unsigned long long labels, bytes, bad, byte_coded;  // (bad: rows the code cannot hold)
+};
+
+// Measure, per range: every row's record size under the image's record code
+// (into d_sz) and the range's counters
+static int measure_range(RowsBuild &rb, Ctx &range, Measure &h) {
+    const RowsImage &im = rb.img;
+    const uint64_t nr = range.tree.num_rows;
+    MBRWT_HIP(hipMemsetAsync(rb.d_acc, 0, 8 * sizeof(unsigned long long), rb.s));
+    hipLaunchKernelGGL(k_rows_measure, dim3(grid256(nr)), dim3(256), 0, rb.s, range.d_nodes,
+                       range.tree.folded ? 1u : 0u, nr, rb.d_sz, rb.d_acc, record_code(im), (const uint32_t *)rb.d_bt,
+                       term_width(im));
+    MBRWT_HIP(hipGetLastError());
+    unsigned long long a[4];
+    if (int rc = read_acc(rb, a, 4)) return rc;
+    h = Measure{a[0], a[1], a[2], a[3]};
+    return MBRWT_OK;
+}
+
+// Decide, on the first range: the record code of the whole image (the rule:
+// rows_plan.hpp); a code that gives way is measured again as what follows it
+static int choose_code(RowsBuild &rb, Ctx &range, Measure &h) {
+    RowsImage &im = rb.img;
+    if (im.term && term_gives_way(h.bad, h.bytes, h.byte_coded)) {
+        im.term = false;
+        im.table3.clear();
+        if (int rc = measure_range(rb, range, h)) return rc;
+    }
+    if (im.nib && nib_gives_way(h.bad, h.bytes, h.byte_coded)) {
+        im.nib = false;
+        if (int rc = measure_range(rb, range, h)) return rc;
+    }
+    return MBRWT_OK;
+}
+
+// k_rows_plan's counters of the measured range under one block shape
+static int plan_range(RowsBuild &rb, Ctx &range, BlockShape bs, PlanCounts &out) {
+    const uint64_t nr = range.tree.num_rows;
+    MBRWT_HIP(hipMemsetAsync(rb.d_acc, 0, 8 * sizeof(unsigned long long), rb.s));
+    hipLaunchKernelGGL(k_rows_plan, dim3(grid256((nr + bs.S - 1) / bs.S)), dim3(256), 0, rb.s, rb.d_sz, nr, bs.B, bs.S,
+                       rb.d_acc);
+    MBRWT_HIP(hipGetLastError());
+    unsigned long long o[3];
+    if (int rc = read_acc(rb, o, 3)) return rc;
+    out = PlanCounts{o[0], o[1], o[2]};
+    return MBRWT_OK;
+}
+
+// the variable-length records of the first range measured: whether they
+// apply (ok), the whole image's bytes, the bytes per row into the plan
+static int measure_var(RowsBuild &rb, Ctx &range, bool forced, RowsPlan &plan, bool &ok, double &image_bytes) {
+    RowsImage &im = rb.img;
+    const uint64_t nr = range.tree.num_rows;
+    uint64_t vb = 0;
+    const int rc = var_measure_range(im, range, rb.vws, &vb, rb.s);
+    if (rc && rc != MBRWT_ERR_UNSUPPORTED) return rc;
+    ok = rc == MBRWT_OK;
+    image_bytes = var_image_bytes(vb, nr, rb.n, rb.align);
+    plan.var_bytes_per_row = (double)vb / (double)nr;
+    // a unit table so large that the decode's LDS cannot hold a mean
+    // tile beside it: AUTO keeps the other layouts (forced: allowed,
+    // every such tile then takes the decode's global path)
+    if (ok && !forced &&
+        !var_lds_fits(im, (double)range.tree.num_relations / std::max<double>(1.0, (double)range.tree.num_rows),
+                      plan.var_bytes_per_row))
+        ok = false;
+    return MBRWT_OK;
+}
+
+// the image's device memory under the plan: directory lines or blocks
+static int alloc_image(RowsBuild &rb, const RowsPlan &plan) {
+    RowsImage &im = rb.img;
+    if (plan.var) {
+        im.var = true;
+        const uint64_t nlines = (rb.n + kVarLineRows - 1) / kVarLineRows;
+        MBRWT_HIP(hipMalloc(&im.var_lines, nlines * 64));
+        MBRWT_HIP(hipMemsetAsync(im.var_lines, 0, nlines * 64, rb.s));
+        return MBRWT_OK;
+    }
+    im.B = plan.block.B;
+    im.S = plan.block.S;
+    im.magic = div_magic(im.S);
+    im.num_blocks = (rb.n + im.S - 1) / im.S;
+    MBRWT_HIP(hipMalloc(&im.blocks, im.num_blocks * im.B));
+    MBRWT_HIP(hipMemsetAsync(im.blocks, 0, im.num_blocks * im.B, rb.s));
+    return MBRWT_OK;
+}
+
+// Decide, on the first range: the layout of the whole image -- every
+// candidate (B, S) planned over the range and priced (the cost model and the
+// choice: rows_plan.hpp), the variable-length records where the blocks cost
+// too much or the build option forces them, the AUTO decline, the
+// MBRWT_BUILD_ROWS_BLOCK override -- then the image's allocation.  Sets rb.plan.
+static int choose_layout(RowsBuild &rb, Ctx &range) {
+    RowsImage &im = rb.img;
+    size_t free_b = 0, total_b = 0;
+    MBRWT_HIP(hipMemGetInfo(&free_b, &total_b));
+    const double budget = (double)free_b - 4.0 * (1ull << 30);
+    std::vector<Cand> cands;
+    for (BlockShape bs : block_candidates(rb.align)) {
+        PlanCounts o;
+        if (int rc = plan_range(rb, range, bs, o)) return rc;
+        cands.push_back(price_candidate(bs, o, range.tree.num_rows, rb.n));
+    }
+    const Choice ch = choose_block(cands, budget, cost_tolerance(rb.footprint == 1, im.uni != 0));
+    RowsPlan plan;
+    const int force_var = build_tuning().rows_var;
+    const bool want_var = force_var == 1 || ch.tmin > kAutoMaxCost;
+    bool var_ok = force_var != 0 && rb.align % kVarLineRows == 0 && var_prepare(range.tree, im);
+    // the lanes per row the decode will run with (the build option, else
+    // automatic): the LDS gate (measure_var) must judge that geometry
+    uint32_t var_G = build_tuning().var_lanes;
+    if (var_G & (var_G - 1) || var_G > 16) var_G = 0;  // (1, 2, 4, 8 or 16; 0: automatic)
+    im.var_G = var_G;
+    double var_mem = kNoFit;
+    if (var_ok && want_var)
+        if (int rc = measure_var(rb, range, force_var == 1, plan, var_ok, var_mem)) return rc;
+    if (var_ok && var_mem <= budget && want_var) {
+        plan.var = true;
+    } else {
+        if (!ch.best) {
+            set_error("row-record image does not fit the device");
+            return MBRWT_ERR_NOMEM;
+        }
+        if (rb.auto_layout && ch.tmin > kAutoMaxCost) {  // (kAutoMaxCost, rows_plan.hpp)
+            set_error("row records too long for the block layout");
+            return MBRWT_ERR_UNSUPPORTED;
+        }
+        plan.block = {ch.best->B, ch.best->S};
+        (void)block_override(build_tuning().rows_block, rb.align, plan.block);  // MBRWT_BUILD_ROWS_BLOCK
+    }
+    if (int rc = alloc_image(rb, plan)) return rc;
+    rb.plan = plan;
+    return MBRWT_OK;
+}
+
+// Write, per range: the range's records into the image under the plan --
+// blocks with their spill entries (the spill area planned and grown first),
+// or the variable-length records (rows_var.hip)
+static int write_range(RowsBuild &rb, Ctx &range, uint64_t row0) {
+    RowsImage &im = rb.img;
+    const uint64_t nr = range.tree.num_rows;
+    if (rb.plan->var) return var_build_range(im, range, row0, rb.vws, rb.s);
+    PlanCounts pc;
+    if (int rc = plan_range(rb, range, rb.plan->block, pc)) return rc;
+    unsigned long long used = 0;
+    MBRWT_HIP(hipMemcpyAsync(&used, im.d_spill_used, sizeof(used), hipMemcpyDeviceToHost, rb.s));
+    MBRWT_HIP(hipStreamSynchronize(rb.s));
+    // a spilled entry stores its offset as u32 16-byte units: the spill area
+    // addresses 64 GiB
+    if (used + pc.units >= (1ull << 32)) {
+        set_error("row-record spill area beyond 64 GiB");
+        return MBRWT_ERR_UNSUPPORTED;
+    }
+    // the first range sizes the area for the whole image (extrapolated)
+    const double scale = row0 == 0 ? (double)rb.n / (double)nr : 1.0;
+    if (int rc = ensure_spill(
+            rb, (uint64_t)(used * 16 + pc.units * 16 * scale * (row0 == 0 ? 1.05 : 1.0)) + 16 * pc.units))
+        return rc;
+    im.spilled_rows += pc.spilled;
+    im.long_rows += pc.long_rows;
+    im.spill_bytes += pc.units * 16;
+    hipLaunchKernelGGL(k_rows_write, dim3(grid256((nr + im.S - 1) / im.S)), dim3(256), 0, rb.s, range.d_nodes,
+                       range.tree.folded ? 1u : 0u, nr, rb.d_sz, im.B, im.S, im.blocks + (row0 / im.S) * im.B,
+                       im.spill, im.d_spill_used, record_code(im), (const uint32_t *)rb.d_bt, term_width(im),
+                       term_id_bits(im));
+    MBRWT_HIP(hipGetLastError());
+    MBRWT_HIP(hipStreamSynchronize(rb.s));
+    return MBRWT_OK;
+}
+
+// Records of one range: prepare (once), measure, decide (the first range, for
+// the whole image: record code, then layout), write.
 int rows_build_range(RowsBuild *rbp, Ctx &range, uint64_t row0) {
     if (!rbp) return MBRWT_ERR_NOMEM;
     RowsBuild &rb = *rbp;
@@ -789,312 +1048,86 @@ int rows_build_range(RowsBuild *rbp, Ctx &range, uint64_t row0) {
         set_error("row-record range not aligned");
         return MBRWT_ERR_INVALID;
     }
-    if (im.table.empty()) {
-        if (!build_rwt_table(range.tree, im.table, im.height, im.max_arity) ||
-            !build_rwt2_table(range.tree, im.table2, im.frames, &im.slot_dnode)) {
-            im.table.clear();
-            set_error("tree shape outside the row-record limits (arity <= 64, columns < 2^16, height <= 16, a walk table of <= 8192 words)");
-            return MBRWT_ERR_UNSUPPORTED;
-        }
-        // one-byte masks everywhere (rows_walk6): the root and every internal
-        // or leaf-parent entry of arity <= 8
-        auto ar8 = [](uint32_t e) { return (e >> 30) == 2u || ((e >> 16) & 0x7Fu) <= 8; };
-        im.mask1 = ar8(im.table2[0]);
-        for (size_t i = 4; i < 4 + (size_t)im.table2[1]; ++i) im.mask1 = im.mask1 && ar8(im.table2[i]);
-        im.uni = im.mask1 ? rwt2_uniform_levels(im.table2) : 0u;
-        if (im.uni) append_path_table(im.table2, im.uni);
-        // masks wider than 16 bits (r06: arity up to 64) are read by the tree
-        // odometer and the one-lane walks only: such a tree needs the tree
-        // odometer's depth
-        // (im.max_arity: over the nodes the walk reaches -- record-only
-        // dnodes such as PACKT_IN carry other arities)
-        if (im.max_arity > 16 && im.frames > kRowsOdoLevels) {
-            im.table.clear();
-            set_error("row records: a node wider than 16 children in a tree deeper than the tree odometer (8 levels)");
-            return MBRWT_ERR_UNSUPPORTED;
-        }
-        // nibble-coded masks (MBRWT_BUILD_ROWS_CODE = 1, r06): read by the
-        // path-table odometer and the one-lane walks, so uniform trees of
-        // one-byte masks with a path table only (the others keep bytes)
-        im.nib = build_tuning().rows_code == 1 && im.uni && im.table2.size() > 3 && im.table2[3] != 0;
-        // terminal records (r06; MBRWT_BUILD_ROWS_CODE 0 = AUTO, the default,
-        // or 2): trees of masks up to 16 bits whose terminals fit the fields
-        im.term = false;
-        // (AUTO, code 0: where they are smaller than byte masks -- decided on
-        // the first range below; code 3 forces byte masks)
-        const int code = build_tuning().rows_code;
-        if ((code == 0 || code == 2) && im.max_arity <= 16) {
-            std::vector<uint32_t> bt, term_slot;
-            bool ok = build_term_tables(im.table2, im.table3, bt, term_slot);
-            if (ok) {
-                im.term_dnode.resize(term_slot.size());
-                for (size_t i = 0; i < term_slot.size(); ++i)
-                    im.term_dnode[i] = term_slot[i] < im.slot_dnode.size() ? im.slot_dnode[term_slot[i]] : ~0u;
-                ok = build_work_table(range.tree, im.term_dnode, im.table4);
-            }
-            if (ok) {
-                if (!rb.d_bt) {
-                    if (hipMalloc(&rb.d_bt, bt.size() * 4) != hipSuccess) return hip_fail(hipGetLastError(), "build table");
-                    MBRWT_HIP(hipMemcpy(rb.d_bt, bt.data(), bt.size() * 4, hipMemcpyHostToDevice));
-                }
-                im.term = true;
-            }
-        }
-    }
-    const uint32_t tw = im.term ? im.table3[0] & 0xFFu : 0u, tib = im.term ? (im.table3[0] >> 8) & 0xFFu : 0u;
-    auto code_of = [&]() -> uint32_t { return im.term ? 2u : im.nib ? 1u : 0u; };
+    if (im.table.empty())
+        if (int rc = prepare_tables(rb, range)) return rc;
     if (nr > rb.sz_cap) {
         if (rb.d_sz) MBRWT_HIP(hipFree(rb.d_sz));
         rb.d_sz = nullptr;
         MBRWT_HIP(hipMalloc(&rb.d_sz, nr * sizeof(uint16_t)));
         rb.sz_cap = nr;
     }
-    unsigned long long h[8];
-    auto measure = [&]() -> int {
-        MBRWT_HIP(hipMemsetAsync(rb.d_acc, 0, 8 * sizeof(unsigned long long), rb.s));
-        hipLaunchKernelGGL(k_rows_measure, dim3(build_grid(nr)), dim3(256), 0, rb.s, range.d_nodes,
-                           range.tree.folded ? 1u : 0u, nr, rb.d_sz, rb.d_acc, code_of(), (const uint32_t *)rb.d_bt, tw);
-        MBRWT_HIP(hipGetLastError());
-        return read_acc(rb, h, 4);
-    };
-    if (int rc = measure()) return rc;
-    // nibble codes or terminal records that do not shrink the first range's
-    // records (dense rows: most masks hold several bits), or terminal
-    // fields a row of the range cannot take, give way to bytes for the
-    // whole image
-    if (im.term && !rb.decided && (h[2] || h[1] >= h[3])) {
-        im.term = false;
-        im.table3.clear();
-        if (int rc = measure()) return rc;
-    }
-    if (im.nib && !rb.decided && h[2] == 0 && h[1] >= h[3]) {
-        im.nib = false;
-        if (int rc = measure()) return rc;
-    }
-    if (h[2]) {
+    Measure h;
+    if (int rc = measure_range(rb, range, h)) return rc;
+    const bool first = !rb.plan;  // the first range decides for the whole image
+    if (first)
+        if (int rc = choose_code(rb, range, h)) return rc;
+    if (h.bad) {
         set_error("row record deeper than the build walker supports");
         return MBRWT_ERR_UNSUPPORTED;
     }
-    if (h[0] != range.tree.num_relations) {
+    if (h.labels != range.tree.num_relations) {
         set_error("row records: label count differs from the node image");
         return MBRWT_ERR_DEVICE;
     }
-    if (!im.var) im.record_bytes += h[1];
-    auto plan = [&](uint32_t B, uint32_t S, unsigned long long out[3]) -> int {
-        MBRWT_HIP(hipMemsetAsync(rb.d_acc, 0, 8 * sizeof(unsigned long long), rb.s));
-        hipLaunchKernelGGL(k_rows_plan, dim3(build_grid((nr + S - 1) / S)), dim3(256), 0, rb.s, rb.d_sz, nr, B, S,
-                           rb.d_acc);
-        MBRWT_HIP(hipGetLastError());
-        return read_acc(rb, out, 3);
-    };
-    if (!rb.decided) {
-        // (B, S): the fewest requests per row -- one block read plus one per
-        // spilled row, a 128-byte block costing kCost128 of a 64-byte one
-        // (measured ceilings), a record longer than a block a
-        // direct-pass row (x50) -- among the images that fit the device,
-        // then the smallest within 2 % of that
-        // a 128-byte block costs more than its request (random 128-byte reads
-        // run at 52.6 vs 53.7 G/s, profiles/r03/v01_probe_sweep.json): its
-        // LDS slots halve the traversal's resident waves -- the greedy +
-        // relax shape at 3.7 B rows took 0.859 ms with 128-byte blocks of 3
-        // rows against 0.522 ms with 64-byte blocks of one row
-        // (profiles/r04/v09_tree_odometer/)
-        constexpr double kCost128 = 1.6;
-        size_t free_b = 0, total_b = 0;
-        MBRWT_HIP(hipMemGetInfo(&free_b, &total_b));
-        const double budget = (double)free_b - 4.0 * (1ull << 30);
-        struct Cand {
-            uint32_t B, S;
-            double t, mem;
-        };
-        std::vector<Cand> cands;
-        const double scale = (double)rb.n / (double)nr;
-        for (uint32_t B : {64u, 128u})
-            for (uint32_t S = 1; S <= (B == 64 ? 8u : 15u); ++S) {
-                if (rb.align % S) continue;
-                unsigned long long o[3];
-                if (int rc = plan(B, S, o)) return rc;
-                const double fs = (double)o[0] / nr, fl = (double)o[2] / nr;
-                Cand c{B, S, (B == 128 ? kCost128 : 1.0) * (1.0 + fs + 50.0 * fl),
-                       (double)((rb.n + S - 1) / S) * B + (double)o[1] * 16.0 * scale};
-                cands.push_back(c);
-            }
-        double tmin = 1e300;
-        for (const Cand &c : cands)
-            if (c.mem <= budget) tmin = std::min(tmin, c.t);
-        // the variable-length records (rows_var.hip: uniform trees, ranges
-        // on directory lines): for rows too long for the blocks -- a block
-        // layout costing more than kAutoMaxCost requests per row (most rows
-        // spilled, or records longer than a block) or none that fits.
-        // The build option MBRWT_BUILD_ROWS_VAR = 1 / 0 forces / forbids them.
-        constexpr double kAutoMaxCost = 1.25;
-        const int force_var = build_tuning().rows_var;
-        bool var_ok = force_var != 0 && rb.align % 13 == 0 && var_prepare(range.tree, im);
-        // the lanes per row the decode will run with (the build option, else
-        // automatic): the LDS gate below must judge that geometry
-        uint32_t var_G = build_tuning().var_lanes;
-        if (var_G & (var_G - 1) || var_G > 16) var_G = 0;  // (1, 2, 4, 8 or 16; 0: automatic)
-        im.var_G = var_G;
-        double var_mem = 1e300;
-        if (var_ok && (force_var == 1 || tmin > kAutoMaxCost)) {
-            uint64_t vb = 0;
-            const int rc = var_measure_range(im, range, rb.vws, &vb, rb.s);
-            if (rc && rc != MBRWT_ERR_UNSUPPORTED) return rc;
-            var_ok = rc == MBRWT_OK;
-            var_mem = (double)vb * scale * 1.02 + (double)((rb.n + 12) / 13) * 64.0 + 64.0 * (1 + rb.n / rb.align);
-            rb.var_bytes_per_row = (double)vb / (double)nr;
-            // a unit table so large that the decode's LDS cannot hold a mean
-            // tile beside it: AUTO keeps the other layouts (forced: allowed,
-            // every such tile then takes the decode's global path)
-            if (var_ok && force_var != 1 &&
-                !var_lds_fits(im, (double)range.tree.num_relations / std::max<double>(1.0, (double)range.tree.num_rows),
-                              rb.var_bytes_per_row))
-                var_ok = false;
-        }
-        if (var_ok && var_mem <= budget && (force_var == 1 || tmin > kAutoMaxCost)) {
-            im.var = true;
-            im.var_G = var_G;
-            const uint64_t nlines = (rb.n + 12) / 13;
-            MBRWT_HIP(hipMalloc(&im.var_lines, nlines * 64));
-            MBRWT_HIP(hipMemsetAsync(im.var_lines, 0, nlines * 64, rb.s));
-            rb.decided = true;
-        } else {
-            if (tmin == 1e300) {
-                set_error("row-record image does not fit the device");
-                return MBRWT_ERR_NOMEM;
-            }
-            // layout AUTO keeps the per-node images when the records are long
-            // enough that most rows would take a second (spill) request or the
-            // direct pass and no variable-length layout applies
-            if (rb.auto_layout && tmin > kAutoMaxCost) {
-                set_error("row records too long for the block layout");
-                return MBRWT_ERR_UNSUPPORTED;
-            }
-            // The smallest image within `tol` of the fewest modelled requests.
-            // The model prices a spilled row as a whole second request, which
-            // holds on the odometer's uniform trees (request-bound: C4 with
-            // three rows per block, 0.321 against 0.268 ms, profiles/r05), so
-            // there FAST keeps within 2 %.  Under the tree odometer (greedy +
-            // relax, non-uniform) the reloads overlap the other waves' walks
-            // (20 % of the rows spilled: +2 % kernel time, profiles/r04/v15_*),
-            // so from r05 such trees take the COMPACT tolerance (30 %) by
-            // default: two rows per block, 158.9 GB instead of 236.9 GB at
-            // 3.7 B rows.  MBRWT_BUILD_ROWS_FOOTPRINT = COMPACT takes 30 % always.
-            const bool compact = rb.footprint == 1 || !im.uni;
-            const double tol = compact ? 1.30 : 1.02;
-            const Cand *best = nullptr;
-            for (const Cand &c : cands)
-                if (c.mem <= budget && c.t <= tmin * tol && (!best || c.mem < best->mem)) best = &c;
-            im.B = best->B;
-            im.S = best->S;
-            if (const uint32_t bs = build_tuning().rows_block) {  // MBRWT_BUILD_ROWS_BLOCK: B << 8 | S
-                const uint32_t Bv = bs >> 8, Sv = bs & 0xFFu;
-                if ((Bv == 64 || Bv == 128) && Sv >= 1 && Sv <= (Bv == 64 ? 8u : 15u) && rb.align % Sv == 0) {
-                    im.B = Bv;
-                    im.S = Sv;
-                }
-            }
-            // row / S = umulhi(row, floor(2^64 / S) + 1), exact for rows < 2^59 and S <= 16
-            im.magic = im.S > 1 ? ((uint64_t)((((unsigned __int128)1) << 64) / im.S) + 1) : 0;
-            im.num_blocks = (rb.n + im.S - 1) / im.S;
-            MBRWT_HIP(hipMalloc(&im.blocks, im.num_blocks * im.B));
-            MBRWT_HIP(hipMemsetAsync(im.blocks, 0, im.num_blocks * im.B, rb.s));
-            rb.decided = true;
-        }
-    }
-    if (im.var) return var_build_range(im, range, row0, rb.vws, rb.s);
-    unsigned long long o[3];
-    if (int rc = plan(im.B, im.S, o)) return rc;
-    unsigned long long used = 0;
-    MBRWT_HIP(hipMemcpyAsync(&used, im.d_spill_used, sizeof(used), hipMemcpyDeviceToHost, rb.s));
-    MBRWT_HIP(hipStreamSynchronize(rb.s));
-    // a spilled entry stores its offset as u32 16-byte units: the spill area
-    // addresses 64 GiB
-    if (used + o[1] >= (1ull << 32)) {
-        set_error("row-record spill area beyond 64 GiB");
-        return MBRWT_ERR_UNSUPPORTED;
-    }
-    // the first range sizes the area for the whole image (extrapolated)
-    const double scale = row0 == 0 ? (double)rb.n / (double)nr : 1.0;
-    if (int rc = ensure_spill(rb, (uint64_t)(used * 16 + o[1] * 16 * scale * (row0 == 0 ? 1.05 : 1.0)) + 16 * o[1]))
-        return rc;
-    im.spilled_rows += o[0];
-    im.long_rows += o[2];
-    im.spill_bytes += o[1] * 16;
-    hipLaunchKernelGGL(k_rows_write, dim3(build_grid((nr + im.S - 1) / im.S)), dim3(256), 0, rb.s, range.d_nodes,
-                       range.tree.folded ? 1u : 0u, nr, rb.d_sz, im.B, im.S, im.blocks + (row0 / im.S) * im.B,
-                       im.spill, im.d_spill_used, code_of(), (const uint32_t *)rb.d_bt, tw, tib);
-    MBRWT_HIP(hipGetLastError());
-    MBRWT_HIP(hipStreamSynchronize(rb.s));
-    return MBRWT_OK;
+    if (!im.var) im.record_bytes += h.bytes;
+    if (first)
+        if (int rc = choose_layout(rb, range)) return rc;
+    return write_range(rb, range, row0);
 }
 
 // device bytes the records of `rows` more rows will still allocate (the
 // variable-length records are allocated per range; blocks up front)
 uint64_t rows_build_pending_bytes(const RowsBuild *rb, uint64_t rows) {
-    return rb && rb->img.var ? (uint64_t)(rb->var_bytes_per_row * 1.02 * (double)rows) + (64ull << 20) : 0;
+    return rb && rb->plan && rb->plan->var ? var_pending_bytes(rb->plan->var_bytes_per_row, rows) : 0;
 }
 
-int rows_build_finish(RowsBuild *rbp) {
-    if (!rbp) return MBRWT_ERR_NOMEM;
-    RowsBuild &rb = *rbp;
+// the finished image's tables on the device, its size, its record classes
+static int finish_image(RowsBuild &rb) {
     RowsImage &im = rb.img;
-    int rc = MBRWT_OK;
-    if (!rb.decided) {  // no rows
+    if (!rb.plan) {  // no rows
         set_error("row records of an empty matrix");
-        rc = MBRWT_ERR_UNSUPPORTED;
+        return MBRWT_ERR_UNSUPPORTED;
     }
-    if (!rc && (hipMalloc(&im.d_table, im.table.size() * 4) != hipSuccess ||
-                hipMemcpy(im.d_table, im.table.data(), im.table.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMalloc(&im.d_table2, im.table2.size() * 4) != hipSuccess ||
-                hipMemcpy(im.d_table2, im.table2.data(), im.table2.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
-        rc = hip_fail(hipGetLastError(), "row-record table upload");
-    if (!rc && im.term &&
+    if (hipMalloc(&im.d_table, im.table.size() * 4) != hipSuccess ||
+        hipMemcpy(im.d_table, im.table.data(), im.table.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc(&im.d_table2, im.table2.size() * 4) != hipSuccess ||
+        hipMemcpy(im.d_table2, im.table2.data(), im.table2.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return hip_fail(hipGetLastError(), "row-record table upload");
+    if (im.term &&
         (hipMalloc(&im.d_table3, im.table3.size() * 4) != hipSuccess ||
          hipMemcpy(im.d_table3, im.table3.data(), im.table3.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
          hipMalloc(&im.d_table4, im.table4.size() * 4) != hipSuccess ||
          hipMemcpy(im.d_table4, im.table4.data(), im.table4.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
-        rc = hip_fail(hipGetLastError(), "terminal table upload");
-    if (rc) {
-        rows_build_abort(rbp);
-        return rc;
-    }
+        return hip_fail(hipGetLastError(), "terminal table upload");
     if (im.var) {
         // (+32 zero entries: the decoder's speculative unit reads past the last word)
         if (hipMalloc(&im.d_var_units, (im.var_units.size() + 32) * 4) != hipSuccess ||
             hipMemset(im.d_var_units, 0, (im.var_units.size() + 32) * 4) != hipSuccess ||
             hipMemcpy(im.d_var_units, im.var_units.data(), im.var_units.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
             hipMalloc(&im.d_var_anc, std::max<size_t>(1, im.var_anc.size()) * 4) != hipSuccess ||
-            hipMemcpy(im.d_var_anc, im.var_anc.data(), im.var_anc.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            rc = hip_fail(hipGetLastError(), "variable-length record tables");
-            rows_build_abort(rbp);
-            return rc;
-        }
-        im.bytes = (rb.n + 12) / 13 * 64 + im.var_rec_bytes;
-    } else {
-        if (!im.spill && ensure_spill(rb, 0)) {
-            rows_build_abort(rbp);
-            return MBRWT_ERR_NOMEM;
-        }
-        im.bytes = im.num_blocks * im.B + im.spill_bytes;
+            hipMemcpy(im.d_var_anc, im.var_anc.data(), im.var_anc.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+            return hip_fail(hipGetLastError(), "variable-length record tables");
+        im.bytes = (rb.n + kVarLineRows - 1) / kVarLineRows * 64 + im.var_rec_bytes;
+        return MBRWT_OK;
     }
-    if (!im.var) {  // record classes where rows repeat few distinct records (rows_class.hip)
-        rc = rows_classes_build(im, rb.n, build_tuning().rows_classes, &im.class_sample_distinct, rb.s);
-        if (rc) {
-            rows_build_abort(rbp);
-            return rc;
-        }
-    }
+    if (!im.spill && ensure_spill(rb, 0)) return MBRWT_ERR_NOMEM;
+    im.bytes = im.num_blocks * im.B + im.spill_bytes;
+    // record classes where rows repeat few distinct records (rows_class.hip)
+    return rows_classes_build(im, rb.n, build_tuning().rows_classes, &im.class_sample_distinct, rb.s);
+}
+
+// uploads the tables, moves the image into the context; frees the build
+// whether it succeeds or not
+int rows_build_finish(RowsBuild *rbp) {
+    if (!rbp) return MBRWT_ERR_NOMEM;
+    std::unique_ptr<RowsBuild> rb(rbp);
+    if (int rc = finish_image(*rb)) return rc;
+    RowsImage &im = rb->img;
     im.occ_cap = build_tuning().rows_wgs_per_cu;  // (MBRWT_BUILD_ROWS_WGS_PER_CU: occupancy sweeps)
     im.ready = true;
-    free_rows(rb.top->rows);
-    rb.top->rows = im;
-    rb.img = RowsImage();  // ownership moved
-    if (rb.d_acc) (void)hipFree(rb.d_acc);
-    if (rb.d_sz) (void)hipFree(rb.d_sz);
-    if (rb.d_bt) (void)hipFree(rb.d_bt);
-    var_free_scratch(rb.vws);
-    delete rbp;
+    free_rows(rb->top->rows);
+    rb->top->rows = im;
+    im = RowsImage();  // ownership moved
     return MBRWT_OK;
 }
 
@@ -2356,15 +2389,13 @@ int rows_set_status(uint64_t *d_status, uint64_t need, int rc, hipStream_t s) {
     return MBRWT_OK;
 }
 
-static uint64_t simple_grid(uint64_t n) { return std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 65536)); }
-
 int rows_get_batch(Ctx &c, const uint64_t *d_rows, const uint64_t *d_cols, uint64_t n, uint8_t *d_out, hipStream_t s) {
     if (n == 0) return MBRWT_OK;
     if (c.rows.var) return var_get_batch(c, d_rows, d_cols, n, d_out, s);
     if (c.rows.classes)
         if (int rc = rows_class_map(c, d_rows, n, &d_rows, s)) return rc;
     MBRWT_HIP(hipMemsetAsync(c.d_scalars, 0, 8 * sizeof(uint64_t), s));
-    hipLaunchKernelGGL(k_rows_get, dim3((unsigned)simple_grid(n)), dim3(256), 0, s, view_of(c),
+    hipLaunchKernelGGL(k_rows_get, dim3(grid256(n)), dim3(256), 0, s, view_of(c),
                        (const uint32_t *)walk_table(c.rows), d_rows, d_cols, n, c.tree.num_columns, d_out,
                        reinterpret_cast<unsigned long long *>(c.d_scalars));
     MBRWT_HIP(hipGetLastError());
@@ -2380,7 +2411,7 @@ int rows_count_labels(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_co
     if (c.tree.num_columns) MBRWT_HIP(hipMemsetAsync(d_counts, 0, c.tree.num_columns * sizeof(uint64_t), s));
     MBRWT_HIP(hipMemsetAsync(c.d_scalars, 0, 8 * sizeof(uint64_t), s));
     if (n)
-        hipLaunchKernelGGL(k_rows_count<false>, dim3((unsigned)simple_grid(n)), dim3(256), 0, s, view_of(c),
+        hipLaunchKernelGGL(k_rows_count<false>, dim3(grid256(n)), dim3(256), 0, s, view_of(c),
                            (const uint32_t *)walk_table(c.rows), d_rows, n, reinterpret_cast<unsigned long long *>(d_counts),
                            reinterpret_cast<unsigned long long *>(c.d_scalars), (const uint32_t *)c.rows.d_table4);
     MBRWT_HIP(hipGetLastError());
@@ -2396,7 +2427,7 @@ int rows_count_work(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *visits
         if (int rc = rows_class_map(c, d_rows, n, &d_rows, s)) return rc;
     MBRWT_HIP(hipMemsetAsync(c.d_scalars, 0, 8 * sizeof(uint64_t), s));
     if (n)
-        hipLaunchKernelGGL(k_rows_count<true>, dim3((unsigned)simple_grid(n)), dim3(256), 0, s, view_of(c),
+        hipLaunchKernelGGL(k_rows_count<true>, dim3(grid256(n)), dim3(256), 0, s, view_of(c),
                            (const uint32_t *)walk_table(c.rows), d_rows, n, nullptr,
                            reinterpret_cast<unsigned long long *>(c.d_scalars), (const uint32_t *)c.rows.d_table4);
     MBRWT_HIP(hipGetLastError());

@@ -198,8 +198,6 @@ __global__ __launch_bounds__(256) void k_var_lines(const uint64_t *__restrict__ 
     }
 }
 
-int build_grid(uint64_t items) { return (int)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, 65536)); }
-
 struct U16ToU64 {
     __host__ __device__ __forceinline__ uint64_t operator()(const uint16_t &x) const { return x; }
 };
@@ -226,7 +224,7 @@ int var_build_range(RowsImage &im, const Ctx &range, uint64_t row0, VarScratch &
     }
     MBRWT_HIP(hipMemsetAsync(d_acc, 0, 64, s));
     MBRWT_HIP(hipMemsetAsync(d_units + nr, 0, 2, s));
-    hipLaunchKernelGGL(k_var_measure, dim3(build_grid(nr)), dim3(256), 0, s, range.d_nodes, range.tree.folded ? 1u : 0u,
+    hipLaunchKernelGGL(k_var_measure, dim3(grid256(nr)), dim3(256), 0, s, range.d_nodes, range.tree.folded ? 1u : 0u,
                        nr, im.d_unit_of, im.var_W, d_units, d_cnt, d_acc);
     MBRWT_HIP(hipGetLastError());
     hipcub::TransformInputIterator<uint64_t, U16ToU64, const uint16_t *> it(d_units, U16ToU64());
@@ -256,11 +254,11 @@ int var_build_range(RowsImage &im, const Ctx &range, uint64_t row0, VarScratch &
     im.var_rec_bytes += 4 * units;
     im.record_bytes += 4 * units;
     MBRWT_HIP(hipMemsetAsync(chunk, 0, bytes, s));
-    hipLaunchKernelGGL(k_var_write, dim3(build_grid(nr)), dim3(256), 0, s, range.d_nodes, range.tree.folded ? 1u : 0u,
+    hipLaunchKernelGGL(k_var_write, dim3(grid256(nr)), dim3(256), 0, s, range.d_nodes, range.tree.folded ? 1u : 0u,
                        nr, im.d_unit_of, im.var_W, d_off, reinterpret_cast<uint8_t *>(chunk));
     MBRWT_HIP(hipGetLastError());
     MBRWT_HIP(hipMemsetAsync(d_acc, 0, 64, s));
-    hipLaunchKernelGGL(k_var_lines, dim3(build_grid((nr + kLineRows - 1) / kLineRows)), dim3(256), 0, s, d_off, d_cnt,
+    hipLaunchKernelGGL(k_var_lines, dim3(grid256((nr + kLineRows - 1) / kLineRows)), dim3(256), 0, s, d_off, d_cnt,
                        nr, (uint64_t)(uintptr_t)chunk, im.var_lines + (row0 / kLineRows) * 64, d_acc);
     MBRWT_HIP(hipGetLastError());
     MBRWT_HIP(hipMemcpyAsync(h, d_acc, sizeof(h), hipMemcpyDeviceToHost, s));
@@ -284,7 +282,7 @@ int var_measure_range(RowsImage &im, const Ctx &range, VarScratch &ws, uint64_t 
     }
     unsigned long long *d_acc = reinterpret_cast<unsigned long long *>(ws.acc.buf);
     MBRWT_HIP(hipMemsetAsync(d_acc, 0, 64, s));
-    hipLaunchKernelGGL(k_var_measure, dim3(build_grid(nr)), dim3(256), 0, s, range.d_nodes, range.tree.folded ? 1u : 0u,
+    hipLaunchKernelGGL(k_var_measure, dim3(grid256(nr)), dim3(256), 0, s, range.d_nodes, range.tree.folded ? 1u : 0u,
                        nr, im.d_unit_of, im.var_W, reinterpret_cast<uint16_t *>(ws.units.buf),
                        reinterpret_cast<uint16_t *>(ws.cnt.buf), d_acc);
     MBRWT_HIP(hipGetLastError());
@@ -730,8 +728,6 @@ VarFn var_fn(uint32_t G) {
                      : k_var_decode<16, kVarWpb>;
 }
 
-uint64_t simple_grid(uint64_t n) { return std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 65536)); }
-
 }  // namespace
 
 // lanes per row and the per-wave LDS budget from the image's statistics
@@ -838,7 +834,7 @@ int var_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets
     c.rows_sc_dirty = true;  // until k_var_decode has run
     hipEvent_t e0, e1;
     if ((rc = timing_events(c, d_status != nullptr, &e0, &e1))) return rc;
-    hipLaunchKernelGGL(k_var_locate, dim3((unsigned)simple_grid(n + 1)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_var_locate, dim3(grid256(n + 1)), dim3(256), 0, s, p);
     MBRWT_HIP(hipGetLastError());
     MBRWT_HIP(hipcub::DeviceScan::ExclusiveSum(c.ws_scan.buf, sb, it, d_offsets, n + 1, s));
     if (c.timing) MBRWT_HIP(hipEventRecord(e0, s));
@@ -859,7 +855,7 @@ int var_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets
 int var_get_batch(Ctx &c, const uint64_t *d_rows, const uint64_t *d_cols, uint64_t n, uint8_t *d_out, hipStream_t s) {
     if (n == 0) return MBRWT_OK;
     MBRWT_HIP(hipMemsetAsync(c.d_scalars, 0, 8 * sizeof(uint64_t), s));
-    hipLaunchKernelGGL(k_var_get, dim3((unsigned)simple_grid(n)), dim3(256), 0, s, var_view(c),
+    hipLaunchKernelGGL(k_var_get, dim3(grid256(n)), dim3(256), 0, s, var_view(c),
                        (const uint32_t *)c.rows.d_var_units, d_rows, d_cols, n, c.tree.num_columns, d_out,
                        reinterpret_cast<unsigned long long *>(c.d_scalars));
     MBRWT_HIP(hipGetLastError());
@@ -876,7 +872,7 @@ int var_count(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_counts, ui
     MBRWT_HIP(hipMemsetAsync(c.d_scalars, 0, 8 * sizeof(uint64_t), s));
     if (n) {
         auto fn = work ? k_var_count<true> : k_var_count<false>;
-        hipLaunchKernelGGL(fn, dim3((unsigned)simple_grid(n)), dim3(256), 0, s, var_view(c),
+        hipLaunchKernelGGL(fn, dim3(grid256(n)), dim3(256), 0, s, var_view(c),
                            (const uint32_t *)c.rows.d_var_units, (const uint32_t *)c.rows.d_var_anc, c.rows.uni,
                            (const DevNode *)c.d_nodes, d_rows, n, reinterpret_cast<unsigned long long *>(d_counts),
                            reinterpret_cast<unsigned long long *>(c.d_scalars));
