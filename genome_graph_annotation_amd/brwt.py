@@ -63,6 +63,40 @@ def _top_labels_batch(fn, h, rows, read_offsets, num_top):
         return lo, labs[: need.value], cnts[: need.value]
 
 
+def _labels_batch_device(fn, h, rows_t, read_off_t, presence_ratio, lab_off_t, labels_t, stream):
+    """Device-buffer batched get_labels through `fn` (mbrwt[_multi]_get_labels_batch_device)
+    on torch tensors; returns the label count, raises MBRWTError with .needed
+    on MBRWT_ERR_CAPACITY."""
+    need = C.c_uint64(0)
+    st = getattr(L.lib(), fn)(
+        h, rows_t.data_ptr(), rows_t.numel(), read_off_t.data_ptr(), read_off_t.numel() - 1,
+        float(presence_ratio), lab_off_t.data_ptr(), labels_t.data_ptr() if labels_t is not None else None,
+        labels_t.numel() if labels_t is not None else 0, C.byref(need), stream)
+    if st == L.MBRWT_ERR_CAPACITY:
+        e = L.MBRWTError(st, fn)
+        e.needed = int(need.value)
+        raise e
+    L.check(st, fn)
+    return int(need.value)
+
+
+def _top_labels_batch_device(fn, h, rows_t, read_off_t, num_top, lab_off_t, labels_t, counts_t, stream):
+    """Device-buffer batched get_top_labels through `fn`
+    (mbrwt[_multi]_get_top_labels_batch_device); as _labels_batch_device."""
+    need = C.c_uint64(0)
+    out = labels_t is not None and counts_t is not None
+    st = getattr(L.lib(), fn)(
+        h, rows_t.data_ptr(), rows_t.numel(), read_off_t.data_ptr(), read_off_t.numel() - 1, int(num_top),
+        lab_off_t.data_ptr(), labels_t.data_ptr() if out else None, counts_t.data_ptr() if out else None,
+        min(labels_t.numel(), counts_t.numel()) if out else 0, C.byref(need), stream)
+    if st == L.MBRWT_ERR_CAPACITY:
+        e = L.MBRWTError(st, fn)
+        e.needed = int(need.value)
+        raise e
+    L.check(st, fn)
+    return int(need.value)
+
+
 def tree_desc(tree):
     """mbrwt_tree_desc of a BFS tree dict (keys: num_rows, num_columns,
     num_children, first_child, leaf_column, vec_size, words); returns the
@@ -415,17 +449,8 @@ class BRWTDevice:
         """get_labels(indices, presence_ratio) for many reads (include/mbrwt.h
         mbrwt_get_labels_batch_device); torch device tensors; returns the
         label count (raises MBRWTError with .needed on MBRWT_ERR_CAPACITY)."""
-        need = C.c_uint64(0)
-        st = L.lib().mbrwt_get_labels_batch_device(
-            self._h, rows_t.data_ptr(), rows_t.numel(), read_off_t.data_ptr(), read_off_t.numel() - 1,
-            float(presence_ratio), lab_off_t.data_ptr(), labels_t.data_ptr() if labels_t is not None else None,
-            labels_t.numel() if labels_t is not None else 0, C.byref(need), stream)
-        if st == L.MBRWT_ERR_CAPACITY:
-            e = L.MBRWTError(st, "mbrwt_get_labels_batch_device")
-            e.needed = int(need.value)
-            raise e
-        L.check(st, "mbrwt_get_labels_batch_device")
-        return int(need.value)
+        return _labels_batch_device("mbrwt_get_labels_batch_device", self._h, rows_t, read_off_t, presence_ratio,
+                                    lab_off_t, labels_t, stream)
 
     def get_labels_batch(self, rows, read_offsets, presence_ratio):
         """Host-buffer form (include/mbrwt.h mbrwt_get_labels_batch): numpy in,
@@ -442,18 +467,8 @@ class BRWTDevice:
     def get_top_labels_batch_device(self, rows_t, read_off_t, num_top, lab_off_t, labels_t, counts_t, stream=None):
         """Device-buffer form on torch tensors (labels int32, counts int64);
         returns the label count (raises MBRWTError with .needed on capacity)."""
-        need = C.c_uint64(0)
-        out = labels_t is not None and counts_t is not None
-        st = L.lib().mbrwt_get_top_labels_batch_device(
-            self._h, rows_t.data_ptr(), rows_t.numel(), read_off_t.data_ptr(), read_off_t.numel() - 1, int(num_top),
-            lab_off_t.data_ptr(), labels_t.data_ptr() if out else None, counts_t.data_ptr() if out else None,
-            min(labels_t.numel(), counts_t.numel()) if out else 0, C.byref(need), stream)
-        if st == L.MBRWT_ERR_CAPACITY:
-            e = L.MBRWTError(st, "mbrwt_get_top_labels_batch_device")
-            e.needed = int(need.value)
-            raise e
-        L.check(st, "mbrwt_get_top_labels_batch_device")
-        return int(need.value)
+        return _top_labels_batch_device("mbrwt_get_top_labels_batch_device", self._h, rows_t, read_off_t, num_top,
+                                        lab_off_t, labels_t, counts_t, stream)
 
     def count_work_device(self, rows_t, stream=None):
         v = C.c_uint64(0)
@@ -478,9 +493,11 @@ class BRWTDevice:
 
 
 class BRWTMulti:
-    """One replica per device, get_rows over all of them (include/mbrwt.h
-    "multi-device"): the batch is cut into contiguous slices, one per replica,
-    and reassembled into one CSR."""
+    """One replica per device (include/mbrwt.h "multi-device").  get_rows: the
+    batch is cut into contiguous slices, one per replica, and reassembled into
+    one CSR.  get_labels_batch / get_top_labels_batch: the batch is cut
+    between reads, every replica classifies its reads on its device, and only
+    the reads' labels are gathered."""
 
     def __init__(self, handle, keepalive=None):
         self._h = handle
@@ -559,3 +576,19 @@ class BRWTMulti:
             raise e
         L.check(st, "mbrwt_multi_get_rows_device")
         return int(need.value)
+
+    # -- batched classify: arguments and results as the BRWTDevice methods ------
+    def get_labels_batch(self, rows, read_offsets, presence_ratio):
+        return _labels_batch("mbrwt_multi_get_labels_batch", self._h, rows, read_offsets, presence_ratio)
+
+    def get_top_labels_batch(self, rows, read_offsets, num_top=2**64 - 1):
+        return _top_labels_batch("mbrwt_multi_get_top_labels_batch", self._h, rows, read_offsets, num_top)
+
+    def get_labels_batch_device(self, rows_t, read_off_t, presence_ratio, lab_off_t, labels_t, stream=None):
+        """Tensors on devices[0], ordered on `stream`; complete on return."""
+        return _labels_batch_device("mbrwt_multi_get_labels_batch_device", self._h, rows_t, read_off_t,
+                                    presence_ratio, lab_off_t, labels_t, stream)
+
+    def get_top_labels_batch_device(self, rows_t, read_off_t, num_top, lab_off_t, labels_t, counts_t, stream=None):
+        return _top_labels_batch_device("mbrwt_multi_get_top_labels_batch_device", self._h, rows_t, read_off_t,
+                                        num_top, lab_off_t, labels_t, counts_t, stream)

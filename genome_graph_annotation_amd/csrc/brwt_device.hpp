@@ -404,7 +404,9 @@ class BRWTDevice : public BinaryMatrix {
 // one CSR; point and column queries and serialisation use replica 0.  The
 // reference's `annograph classify` (one process, a ThreadPool,
 // main.cpp:462-497) runs StaticBinRelAnnotator<BRWTMultiDevice> to use every
-// GPU of the node.
+// GPU of the node: its get_labels / get_top_labels batches are cut between
+// reads and classified on the replicas' devices (labels_batch_csr,
+// top_labels_batch_csr), not counted on the host from get_rows.
 class BRWTMultiDevice : public BinaryMatrix {
   public:
     BRWTMultiDevice() = default;
@@ -477,6 +479,29 @@ class BRWTMultiDevice : public BinaryMatrix {
             return;
         }
     }
+    // batched classify on every replica (mbrwt_multi_get[_top]_labels_batch):
+    // the reads are cut among the replicas and only their labels come back;
+    // false on MBRWT_ERR_UNSUPPORTED (more columns than the device kernels
+    // hold), so the annotator answers read by read as with BRWTDevice
+    bool labels_batch_csr(const std::vector<Row> &rows, const std::vector<uint64_t> &read_offsets, double ratio,
+                          std::vector<uint64_t> *lab_off, std::vector<uint32_t> *labels) const override {
+        return classify_csr(rows, read_offsets, lab_off, labels, nullptr, "BRWTMultiDevice::get_labels_batch",
+                            [&](uint64_t cap, uint64_t *need) {
+                                return mbrwt_multi_get_labels_batch(m_.get(), rows.data(), rows.size(),
+                                                                    read_offsets.data(), read_offsets.size() - 1, ratio,
+                                                                    lab_off->data(), labels->data(), cap, need);
+                            });
+    }
+    bool top_labels_batch_csr(const std::vector<Row> &rows, const std::vector<uint64_t> &read_offsets,
+                              uint64_t num_top, std::vector<uint64_t> *lab_off, std::vector<uint32_t> *labels,
+                              std::vector<uint64_t> *counts) const override {
+        return classify_csr(rows, read_offsets, lab_off, labels, counts, "BRWTMultiDevice::get_top_labels_batch",
+                            [&](uint64_t cap, uint64_t *need) {
+                                return mbrwt_multi_get_top_labels_batch(
+                                    m_.get(), rows.data(), rows.size(), read_offsets.data(), read_offsets.size() - 1,
+                                    num_top, lab_off->data(), labels->data(), counts->data(), cap, need);
+                            });
+    }
     // BRWT::load onto every replica (mbrwt_multi_load); false on a bad stream
     bool load(std::istream &in) override {
         try {
@@ -507,6 +532,36 @@ class BRWTMultiDevice : public BinaryMatrix {
     }
 
   private:
+    // the grow-and-retry loop of BRWTDevice::get[_top]_labels_batch_csr around
+    // call(cap, &need); counts = nullptr for get_labels
+    template <class Call>
+    bool classify_csr(const std::vector<Row> &rows, const std::vector<uint64_t> &read_offsets,
+                      std::vector<uint64_t> *lab_off, std::vector<uint32_t> *labels, std::vector<uint64_t> *counts,
+                      const char *where, Call &&call) const {
+        if (read_offsets.empty()) throw std::invalid_argument("read_offsets needs n_reads + 1 entries");
+        lab_off->assign(read_offsets.size(), 0);
+        labels->clear();
+        if (counts) counts->clear();
+        if (!m_) {
+            if (!rows.empty()) throw std::out_of_range(std::string(where) + " on an empty BRWT");
+            return true;
+        }
+        uint64_t cap = std::max<uint64_t>(16, 4 * rows.size()), need = 0;
+        for (;;) {
+            labels->resize(cap);
+            if (counts) counts->resize(cap);
+            const int st = call(cap, &need);
+            if (st == MBRWT_ERR_CAPACITY) {
+                cap = need;
+                continue;
+            }
+            if (st == MBRWT_ERR_UNSUPPORTED) return false;  // per-read fallback
+            check_status(st, where);
+            labels->resize(need);
+            if (counts) counts->resize(need);
+            return true;
+        }
+    }
     mbrwt_ctx *r0() const { return mbrwt_multi_replica(m_.get(), 0); }
     struct Deleter {
         void operator()(mbrwt_multi *m) const { mbrwt_multi_destroy(m); }

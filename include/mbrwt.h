@@ -300,6 +300,26 @@ int mbrwt_rows_classes(const mbrwt_ctx *ctx, uint64_t out[4]);
  * (main.cpp:462-497): this is how its host drives every GPU of a node.
  * mbrwt_multi_replica gives replica i's context (point / column queries,
  * properties, export); it is owned by the multi handle.
+ *
+ * What classify itself calls -- get_labels(indices, presence_ratio)
+ * (main.cpp:193) and get_top_labels(indices, num_top) (main.cpp:177) -- runs
+ * on every replica end to end: mbrwt_multi_get_labels_batch[_device] and
+ * mbrwt_multi_get_top_labels_batch[_device] take the arguments of
+ * mbrwt_get_labels_batch[_device] / mbrwt_get_top_labels_batch[_device]
+ * (below) and return their output, order, tie order, errors and capacity
+ * protocol over the whole batch (*labels_needed = the total of all
+ * replicas).  The batch is cut between reads, not rows: replica r classifies
+ * the whole reads [b_r, b_{r+1}), b_0 = 0, b_k = n_reads, and for 0 < r < k
+ *     b_r = the first read whose first row offset is >= ceil(r * n_rows / k),
+ * so no replica holds more than n_rows / k rows plus the longest read; a
+ * replica may get no read; reads without rows at the front of the batch stay
+ * on replica 0, those at the back on replica k - 1.  The read offsets are
+ * validated as a whole (first 0, ascending, last n_rows) before any replica
+ * runs: MBRWT_ERR_INVALID.  Only the rows (in) and each read's labels (out)
+ * cross devices.  Device forms: inputs and outputs on devices[0], ordered on
+ * `stream`; the outputs are complete on return.  When several replicas fail,
+ * the status and message are those of the lowest one.  Calls on one handle
+ * are serialised.
  */
 typedef struct mbrwt_multi mbrwt_multi;
 int mbrwt_multi_create(const mbrwt_tree_desc *desc, const int *devices, int n, mbrwt_multi **out);
@@ -313,6 +333,21 @@ int mbrwt_multi_get_rows(mbrwt_multi *m, const uint64_t *rows, uint64_t n, uint6
                          uint64_t cols_cap, uint64_t *cols_needed);
 int mbrwt_multi_get_rows_device(mbrwt_multi *m, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets,
                                 uint32_t *d_cols, uint64_t cols_cap, uint64_t *cols_needed, void *stream);
+int mbrwt_multi_get_labels_batch(mbrwt_multi *m, const uint64_t *rows, uint64_t n_rows, const uint64_t *read_offsets,
+                                 uint64_t n_reads, double presence_ratio, uint64_t *label_offsets, uint32_t *labels,
+                                 uint64_t labels_cap, uint64_t *labels_needed);
+int mbrwt_multi_get_labels_batch_device(mbrwt_multi *m, const uint64_t *d_rows, uint64_t n_rows,
+                                        const uint64_t *d_read_offsets, uint64_t n_reads, double presence_ratio,
+                                        uint64_t *d_label_offsets, uint32_t *d_labels, uint64_t labels_cap,
+                                        uint64_t *labels_needed, void *stream);
+int mbrwt_multi_get_top_labels_batch(mbrwt_multi *m, const uint64_t *rows, uint64_t n_rows,
+                                     const uint64_t *read_offsets, uint64_t n_reads, uint64_t num_top,
+                                     uint64_t *label_offsets, uint32_t *labels, uint64_t *counts, uint64_t labels_cap,
+                                     uint64_t *labels_needed);
+int mbrwt_multi_get_top_labels_batch_device(mbrwt_multi *m, const uint64_t *d_rows, uint64_t n_rows,
+                                            const uint64_t *d_read_offsets, uint64_t n_reads, uint64_t num_top,
+                                            uint64_t *d_label_offsets, uint32_t *d_labels, uint64_t *d_counts,
+                                            uint64_t labels_cap, uint64_t *labels_needed, void *stream);
 
 /* ---- files: the reference's BRWT stream (the matrix of a .brwt.annodbg) ----
  * An owned tree description (host memory).  Byte formats of sdsl-lite /

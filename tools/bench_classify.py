@@ -5,6 +5,9 @@ Kingsford-shaped Multi-BRWT of bench.py (3.7 B x 2,652, d = 0.3 %, device
 generated).  Synthetic reads of --read-len k-mer rows drawn uniformly at random
 (rows of a real read are correlated; i.i.d. rows are the label-richest case for
 ratio 0).  One step = one call over --reads reads, device-resident in and out.
+--devices 0,1,... runs the same batch through BRWTMulti (a replica per entry,
+mbrwt_multi_get[_top]_labels_batch_device; buffers on the first device); a
+device listed more than once shows the cost of the plumbing, not scaling.
 Parity: every read of the batch against the reference semantics applied to
 the batch's own get_rows output (np.bincount + the std::ceil threshold)."""
 import argparse
@@ -29,12 +32,18 @@ ap.add_argument("--read-len", type=int, default=80)
 ap.add_argument("--ratio", type=float, default=0.0)
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--top", type=int, default=-1, help="get_top_labels(indices, TOP) instead (classify --count-labels)")
+ap.add_argument("--devices", default="", help="comma-separated devices: one replica each through BRWTMulti")
 a = ap.parse_args()
 
-from genome_graph_annotation_amd import BRWTDevice, _lib as L  # noqa: E402
+from genome_graph_annotation_amd import BRWTDevice, BRWTMulti, _lib as L  # noqa: E402
 
-dev = torch.device("cuda", 0)
-mat = BRWTDevice.synthetic(a.rows, a.cols, a.density, 8, 42)
+devices = [int(d) for d in a.devices.split(",")] if a.devices else None
+dev = torch.device("cuda", devices[0] if devices else 0)
+torch.cuda.set_device(dev)
+if devices:
+    mat = BRWTMulti.synthetic(a.rows, a.cols, a.density, 8, 42, devices=devices)
+else:
+    mat = BRWTDevice.synthetic(a.rows, a.cols, a.density, 8, 42)
 rng = np.random.default_rng(3)
 n = a.reads * a.read_len
 rows_np = rng.integers(0, a.rows, n, dtype=np.uint64)
@@ -88,11 +97,11 @@ for r in range(a.reads):
         break
 what = ("get_top_labels(indices, num_top)" if top else "get_labels(indices, presence_ratio)")
 print(json.dumps({
-    "metric": f"batched {what} on Multi-BRWT (classify), reads/s",
+    "metric": f"batched {what} on Multi-BRWT (classify{', BRWTMulti' if devices else ''}), reads/s",
     "value": a.reads / el, "unit": "reads/s", "rows_per_s": n / el, "ms_per_step": el * 1e3,
     "config": {"rows": a.rows, "columns": a.cols, "density": a.density, "reads": a.reads,
                "read_len": a.read_len, "presence_ratio": None if top else a.ratio,
-               "num_top": a.top if top else None, "labels_out": int(got)},
+               "num_top": a.top if top else None, "labels_out": int(got), "devices": devices},
     "parity": (f"every read identical to {'annotate.cpp:57-83' if top else 'annotate_static.cpp:71-94'} "
                "applied to the batch's get_rows"
                if ok else "MISMATCH"),
