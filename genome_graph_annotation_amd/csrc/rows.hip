@@ -540,7 +540,9 @@ __global__ __launch_bounds__(256) void k_rows_measure(const DevNode *nodes, uint
                     : 0x8000u;  // (a row the fields cannot hold: bad)
         }
         bytes1 += b1;
-        if (L == ~0u || b >= 0x8000) {
+        // (a row of >= 2^15 labels: the temp regions carry a row's count in
+        // 15 bits beside the long-record flag, k_traverse_rows / k_compact_tiles)
+        if (L == ~0u || b >= 0x8000 || L > 0x7FFFu) {
             ++bad;
             sz[r] = 0x7FFF;
             continue;
@@ -1062,7 +1064,7 @@ int rows_build_range(RowsBuild *rbp, Ctx &range, uint64_t row0) {
     if (first)
         if (int rc = choose_code(rb, range, h)) return rc;
     if (h.bad) {
-        set_error("row record deeper than the build walker supports");
+        set_error("row record deeper than the build walker supports, or a row of more than 32,767 labels");
         return MBRWT_ERR_UNSUPPORTED;
     }
     if (h.labels != range.tree.num_relations) {

@@ -172,7 +172,9 @@ int mbrwt_ctx_clone(mbrwt_ctx *src, mbrwt_ctx **out);
  *          and a record walk; the rank1 remaps are resolved at build time.
  *          Trees with arity <= 64 (r06; 16 before: nodes wider than 16
  *          need a tree of at most 8 internal levels), < 2^16 columns (2^15
- *          before), height <= 16.  Built one
+ *          before), height <= 16, at most 32,767 labels in any one row (a
+ *          row's count travels in 15 bits between the traversal and the
+ *          CSR; the variable-length records have the same bound).  Built one
  *          range of rows at a time, so rows >= 2^32 need no row shards.
  *          get_column scans the records; mbrwt_tree_export rebuilds every
  *          index column from the records (so BinaryMatrix::serialize works).
