@@ -312,6 +312,13 @@ bool build_rwt_table(const Tree &tree, std::vector<uint32_t> &table, uint32_t &h
 bool build_rwt2_table(const Tree &tree, std::vector<uint32_t> &table2, uint32_t &frames,
                       std::vector<uint32_t> *slot_dnode = nullptr);
 uint32_t rwt2_uniform_levels(const std::vector<uint32_t> &table2);
+// the other walk tables (rows_tables.cpp, where their layouts are): the path
+// table of a uniform tree of K levels appended to its RWT2 table; the TT and
+// build tables of terminal records; the work table of their V accounting
+void append_path_table(std::vector<uint32_t> &table2, uint32_t K);
+bool build_term_tables(const std::vector<uint32_t> &table2, std::vector<uint32_t> &tt, std::vector<uint32_t> &bt,
+                       std::vector<uint32_t> &term_slot);
+bool build_work_table(const Tree &tree, const std::vector<uint32_t> &term_dnode, std::vector<uint32_t> &wt);
 // the thread's build layout (mbrwt_set_build_option; AUTO when unset)
 int build_layout();
 void set_build_layout(int layout);
@@ -434,7 +441,7 @@ struct Ctx {
     bool released = false;
 };
 
-// row-record image construction (rows.hip): records of the rows [row0, row0 +
+// row-record image construction (rows_build.hip): records of the rows [row0, row0 +
 // range.num_rows) written from the node image of `range` (a context over
 // those rows, tables uploaded); the first range measured decides the block
 // size and rows per block (S must divide `align`: every later range starts at
@@ -517,6 +524,9 @@ int timing_events(Ctx &c, bool async, hipEvent_t *e0, hipEvent_t *e1);
 // the kernel time (ev0..ev1) taken, the status mapped to a return code + message
 //   row-record block {total, status}; `fallback`: the message of any other status
 int finish_rows_call(Ctx &c, uint64_t *needed, const char *fallback, hipStream_t s);
+//   a record point query's counters (get_batch, count_labels, the work count):
+//   [2] bit 0 -> MBRWT_ERR_RANGE, else [3] visits and [4] labels where asked
+int finish_record_call(Ctx &c, hipStream_t s, uint64_t *visits = nullptr, uint64_t *labels = nullptr);
 //   node-image block {total, overflow rows, error bits}
 int finish_nodes_call(Ctx &c, uint64_t cap, uint64_t *needed, uint64_t *overflow, hipStream_t s);
 // the node protocol's error bits: 1 -> MBRWT_ERR_RANGE, 2 -> MBRWT_ERR_UNSUPPORTED (+ *msg for set_error)

@@ -25,6 +25,7 @@
 #include "device_access.hpp"
 #include "mbrwt_internal.hpp"
 #include "pack_block.hpp"
+#include "wave_scan.hpp"
 
 namespace mbrwt {
 
@@ -1060,12 +1061,6 @@ struct P2wParams {
     unsigned long long *scalars;  // [1] overflow rows, [2] error flags
 };
 
-__device__ __forceinline__ void wave_sync_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // (A register prefetch of a group's next block measured +1 % at 8 waves per
 // SIMD and -7 % at 6: removed)
 template <bool NT, typename LT = uint32_t>
@@ -1162,7 +1157,7 @@ __global__ __launch_bounds__(256, 8) void k_traverse_p2w(P2wParams p) {
             if (c == 0) gfirst[g] = pre;
             if (lane == 60) gfirst[16] = pre + ng;
         }
-        wave_sync_lds();
+        wave_sync();
         const uint32_t T = __builtin_amdgcn_readfirstlane(gfirst[16]);
 
         // ---- rounds: group g resolves item ib + g ----
@@ -1179,17 +1174,17 @@ __global__ __launch_bounds__(256, 8) void k_traverse_p2w(P2wParams p) {
             const uint32_t lgs = roots[4 * k + 2], aidx = roots[4 * k + 3];
             const uint32_t t = j & ((1u << lgs) - 1u);
             if (act) ((AS_LDS u32x4_t *)pk)[c] = u32x4_t{q.x, q.y, q.z, q.w};
-            wave_sync_lds();
+            wave_sync();
             uint32_t s = act ? pb[t] : 0u;
             if (act && pb[0] == 0) {
                 // spilled block: copy the position's record into the group's
                 // slot (list = u16 start[S+1], then the records; <= 64 bytes)
                 const uint64_t la = ((uint64_t)pk[3] << 32) | pk[2];
                 const uint32_t s0 = gld_at<uint16_t>(la + 2ull * t), len = gld_at<uint16_t>(la + 2ull * t + 2) - s0;
-                wave_sync_lds();  // every lane has read the list address
+                wave_sync();  // every lane has read the list address
                 AS_LDS uint8_t *pw = (AS_LDS uint8_t *)pk;
                 for (uint32_t o = c; o < len; o += 4) pw[o] = gld_at<uint8_t>(la + s0 + o);
-                wave_sync_lds();
+                wave_sync();
                 s = 0;
             }
             // record walk, part 1: this lane's children A = 2c, 2c+1 of the
@@ -1225,7 +1220,7 @@ __global__ __launch_bounds__(256, 8) void k_traverse_p2w(P2wParams p) {
             if (direct) {
                 for (uint32_t q2 = flushed + lane; q2 < running; q2 += 64)
                     if (q2 < p.C) gst(out + q2, (LT)ring[q2 & smask]);
-                wave_sync_lds();
+                wave_sync();
             }
             // part 2: the labels, in the record's (pre-)order
             uint32_t pos = ibase + lofs;
@@ -1250,16 +1245,16 @@ __global__ __launch_bounds__(256, 8) void k_traverse_p2w(P2wParams p) {
             } else {
                 const uint32_t F = running & ~63u;  // complete 64-label units
                 if (F > flushed) {
-                    wave_sync_lds();
+                    wave_sync();
                     for (uint32_t q2 = flushed + lane; q2 < F; q2 += 64)
                         if (q2 < p.C) gst(out + q2, (LT)ring[q2 & smask]);
                     flushed = F;
                 }
             }
-            wave_sync_lds();  // the group's block slot and the ring are reused
+            wave_sync();  // the group's block slot and the ring are reused
         }
         if (lane == 0) ipos[T] = running;
-        wave_sync_lds();
+        wave_sync();
         for (uint32_t q2 = flushed + lane; q2 < running; q2 += 64)
             if (q2 < p.C) gst(out + q2, (LT)ring[q2 & smask]);
         if (c == 0 && g < nr) gst(p.counts + r0 + g, (uint32_t)(ipos[gfirst[g + 1]] - ipos[gfirst[g]]));
@@ -1270,7 +1265,7 @@ __global__ __launch_bounds__(256, 8) void k_traverse_p2w(P2wParams p) {
             k0 = (unsigned long long)__shfl((long long)k0, 0, 64);
             if (c == 0 && g < nr) gst(p.ovf_list + k0 + g, (uint32_t)(r0 + g));
         }
-        wave_sync_lds();
+        wave_sync();
     }
 }
 
@@ -1497,7 +1492,7 @@ __global__ __launch_bounds__(64 * kPtwWpb) void k_traverse_ptw(P2wParams p) {
             }
             if (lane == 60) gfirst[16] = pre + ng;
         }
-        wave_sync_lds();
+        wave_sync();
         const uint32_t T = __builtin_amdgcn_readfirstlane(gfirst[16]);
 
         // ---- rounds: lane L resolves item ib + L ----
@@ -1521,7 +1516,7 @@ __global__ __launch_bounds__(64 * kPtwWpb) void k_traverse_ptw(P2wParams p) {
 #pragma unroll
             for (uint32_t h = 0; h < 4; ++h)
                 ((AS_LDS u32x4_t *)(slots + 16 * (4 * g + h)))[c] = u32x4_t{q[h].x, q[h].y, q[h].z, q[h].w};
-            wave_sync_lds();
+            wave_sync();
             const uint32_t i = ib + lane;
             const bool act = i < T;
             uint32_t j = 0, k = 0;
@@ -1572,7 +1567,7 @@ __global__ __launch_bounds__(64 * kPtwWpb) void k_traverse_ptw(P2wParams p) {
             if (direct) {
                 for (uint32_t q2 = flushed + lane; q2 < running; q2 += 64)
                     if (q2 < p.C) gst(out + q2, (PtwLabel)ring[q2 & smask]);
-                wave_sync_lds();
+                wave_sync();
             }
             if (!direct) {
                 ptw_walk_wave<MAXD>(pb, s + 1, ent, blk, ntab, etab, ring, smask, ibase, overflow);
@@ -1588,13 +1583,13 @@ __global__ __launch_bounds__(64 * kPtwWpb) void k_traverse_ptw(P2wParams p) {
             } else {
                 const uint32_t F = running & ~63u;  // complete 64-label units
                 if (F > flushed) {
-                    wave_sync_lds();
+                    wave_sync();
                     for (uint32_t q2 = flushed + lane; q2 < F; q2 += 64)
                         if (q2 < p.C) gst(out + q2, (PtwLabel)ring[q2 & smask]);
                     flushed = F;
                 }
             }
-            wave_sync_lds();  // the slots and the ring are reused
+            wave_sync();  // the slots and the ring are reused
         }
         for (uint32_t q2 = flushed + lane; q2 < running; q2 += 64)
             if (q2 < p.C) gst(out + q2, (PtwLabel)ring[q2 & smask]);
@@ -1606,7 +1601,7 @@ __global__ __launch_bounds__(64 * kPtwWpb) void k_traverse_ptw(P2wParams p) {
             k0 = (unsigned long long)__shfl((long long)k0, 0, 64);
             if (lane < nr) gst(p.ovf_list + k0 + lane, (uint32_t)(r0 + lane));
         }
-        wave_sync_lds();
+        wave_sync();
     }
     if (overflow) atomicOr(&p.scalars[2], 2ull);
 }
@@ -1789,10 +1784,6 @@ __global__ __launch_bounds__(kCompactTile) void k_compact(const uint64_t *__rest
         __syncthreads();
     }
 }
-
-struct U32ToU64 {
-    __host__ __device__ __forceinline__ uint64_t operator()(const uint32_t &x) const { return x; }
-};
 
 // Point queries: walk the column's root-to-leaf path (BRWT::get, BRWT.cpp:9-24).
 __global__ __launch_bounds__(256) void k_get(const DevNode *__restrict__ nodes, const uint8_t *__restrict__ col_path,
@@ -2099,6 +2090,16 @@ int finish_rows_call(Ctx &c, uint64_t *needed, const char *fallback, hipStream_t
     }
 }
 
+int finish_record_call(Ctx &c, hipStream_t s, uint64_t *visits, uint64_t *labels) {
+    MBRWT_HIP(hipGetLastError());
+    MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    MBRWT_HIP(hipStreamSynchronize(s));
+    if (c.h_scalars[2] & 1) return MBRWT_ERR_RANGE;
+    if (visits) *visits = c.h_scalars[3];
+    if (labels) *labels = c.h_scalars[4];
+    return MBRWT_OK;
+}
+
 int node_error_code(uint64_t bits, const char **msg) {
     if (bits & 1) {
         if (msg) *msg = "row out of range";
@@ -2211,7 +2212,7 @@ static int run_get_rows_p2w(Ctx &c, const RowblockKernel &kr, const uint64_t *d_
     uint32_t *d_counts = reinterpret_cast<uint32_t *>(c.ws_counts.buf);
     uint32_t *d_block_counts = d_counts + bc_off;
     uint64_t *d_block_offsets = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(c.ws_counts.buf) + bo_off);
-    hipcub::TransformInputIterator<uint64_t, U32ToU64, const uint32_t *> it(d_block_counts, U32ToU64());
+    hipcub::TransformInputIterator<uint64_t, Widen<uint32_t>, const uint32_t *> it(d_block_counts, Widen<uint32_t>());
     size_t scan_bytes = 0;
     MBRWT_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, it, d_block_offsets, nb + 1, s));
     if ((rc = ensure(c.ws_scan, scan_bytes))) return rc;
@@ -2332,8 +2333,8 @@ int run_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets
     uint32_t *d_chunk_counts = d_counts + cc_off;
     uint64_t *d_chunk_offsets = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(c.ws_counts.buf) + co_off);
     // scan input: the row counts (general kernels) or the chunk counts (fast2)
-    hipcub::TransformInputIterator<uint64_t, U32ToU64, const uint32_t *> it(fn.fast ? d_chunk_counts : d_counts,
-                                                                            U32ToU64());
+    hipcub::TransformInputIterator<uint64_t, Widen<uint32_t>, const uint32_t *> it(fn.fast ? d_chunk_counts : d_counts,
+                                                                            Widen<uint32_t>());
     uint64_t *scan_out = fn.fast ? d_chunk_offsets : d_offsets;
     const uint64_t scan_n = (fn.fast ? nch : n) + 1;
     size_t scan_bytes = 0;

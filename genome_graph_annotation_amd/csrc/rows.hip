@@ -1,6 +1,7 @@
 // rows.hip -- ROW RECORDS: the BRWT's index bits regrouped by row, and the
 // row-record query kernels (layout in mbrwt_internal.hpp "ROW RECORDS",
-// DESIGN.md §4/§5).
+// DESIGN.md §4/§5; the image is built in rows_build.hip from the walk tables
+// of rows_tables.cpp).
 //
 // The reference answers get_row(r) (BRWT.cpp:26-53) by a descent that reads,
 // at every internal node u it reaches, the index bits of u's children at
@@ -13,17 +14,6 @@
 // record over the tree's shape (the RWT table, in LDS): the rank1 remaps are
 // resolved once, when the image is built from a node image (any of its
 // layouts), not per query.
-//
-// Build (rows_build_*): rows_build_range takes one range of rows through
-// named steps.  prepare_tables (once): the walk tables and the candidate
-// record code.  measure_range: one thread per row walks the node image and
-// measures its record (k_rows_measure).  On the first range, for the whole
-// image: choose_code settles the record code and choose_layout the block
-// size B and rows per block S from the records' sizes (k_rows_plan: spilled
-// rows and spill bytes per candidate) or the variable-length records, and
-// allocates the image; the rules and the cost model are pure host code in
-// rows_plan.hpp.  write_range: one thread per block writes the block and its
-// spill entries (k_rows_write).  RowsBuild's destructor is the one release.
 //
 // Query (rows_get_rows): k_traverse_rows -- one wave per tile of 64 query
 // rows: the 64 blocks are read as coalesced 16-byte quarters (one request per
@@ -41,1098 +31,15 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <memory>
-#include <optional>
 
 #include "device_access.hpp"
 #include "mbrwt_internal.hpp"
 #include "pack_block.hpp"
-#include "rows_emit.hpp"
-#include "rows_plan.hpp"
 #include "rows_record.hpp"
+#include "rows_select.hpp"
 #include "wave_scan.hpp"
 
 namespace mbrwt {
-
-// ------------------------------------------------------------------------
-// layout selection
-// ------------------------------------------------------------------------
-static thread_local int g_build_layout = LAYOUT_AUTO;  // AUTO: the automatic choice
-static thread_local BuildTuning g_build_tuning;        // MBRWT_BUILD_ROWS_VAR .. _ROWS_WGS_PER_CU
-BuildTuning &build_tuning() { return g_build_tuning; }
-void set_build_tuning(const BuildTuning &t) { g_build_tuning = t; }
-
-int build_layout() { return g_build_layout; }
-
-void set_build_layout(int layout) { g_build_layout = layout; }
-int thread_build_layout() { return g_build_layout; }
-static thread_local int g_rows_footprint = 0;  // MBRWT_ROWS_FAST
-void set_rows_footprint(int v) { g_rows_footprint = v; }
-int rows_footprint() { return g_rows_footprint; }
-
-// ------------------------------------------------------------------------
-// RWT table
-// ------------------------------------------------------------------------
-bool build_rwt_table(const Tree &tree, std::vector<uint32_t> &table, uint32_t &height, uint32_t &max_arity) {
-    table.clear();
-    height = 0;
-    max_arity = 0;
-    const auto &N = tree.nodes;
-    if (N.size() < 2) return false;
-    // the logical root: the folded root's children hang off dnode 0
-    const bool folded = tree.folded;
-    const uint32_t root = folded ? 0u : 1u;
-    if (!folded && N[0].arity != 1) return false;
-    if (N[root].kind == KIND_LEAF || N[root].arity == 0) return false;  // one-column tree
-    auto column_of = [&](const DevNode &d) { return tree.label_perm.empty() ? d.label : tree.label_perm[d.label]; };
-    std::vector<uint32_t> inner{root}, level{1};
-    std::vector<uint32_t> local(N.size(), UINT32_MAX);
-    local[root] = 0;
-    for (size_t h = 0; h < inner.size(); ++h) {
-        const DevNode &v = N[inner[h]];
-        height = std::max(height, level[h]);
-        if (v.arity == 0 || v.arity > kRowsMaxArity) return false;
-        max_arity = std::max<uint32_t>(max_arity, v.arity);
-        for (uint32_t c = 0; c < v.arity; ++c) {
-            const uint32_t w = v.first_child + c;
-            if (w >= N.size()) return false;
-            if (N[w].kind != KIND_LEAF) {
-                local[w] = (uint32_t)inner.size();
-                inner.push_back(w);
-                level.push_back(level[h] + 1);
-            }
-        }
-    }
-    if (height > kRowsMaxHeight || inner.size() >= 0x8000) return false;
-    std::vector<uint32_t> nodew(inner.size());
-    std::vector<uint32_t> ent;  // (r06: u32 entries -- columns up to 2^16; u16 with 15-bit columns before)
-    for (size_t i = 0; i < inner.size(); ++i) {
-        const DevNode &v = N[inner[i]];
-        if (ent.size() + v.arity > 0xFFFFFF) return false;
-        nodew[i] = (uint32_t)ent.size() | ((uint32_t)v.arity << 24);
-        for (uint32_t c = 0; c < v.arity; ++c) {
-            const DevNode &w = N[v.first_child + c];
-            if (w.kind == KIND_LEAF) {
-                const uint32_t col = column_of(w);
-                if (col >= 0x10000) return false;  // (the label stage and temp regions hold u16 labels)
-                ent.push_back(0x80000000u | col);
-            } else {
-                ent.push_back(local[v.first_child + c]);
-            }
-        }
-    }
-    const size_t nI = inner.size(), nE = ent.size();
-    const size_t words = 4 + nI + nE;
-    // (the RWT table stays in global memory -- the one-lane walks read it
-    // there -- so only the LDS-staged RWT2 table has kRowsMaxTableWords)
-    if (words > (1u << 22)) return false;
-    table.assign(words, 0);
-    table[0] = (uint32_t)nI;
-    table[1] = (uint32_t)nE;
-    table[2] = height;
-    std::memcpy(&table[4], nodew.data(), nI * 4);
-    std::memcpy(&table[4 + nI], ent.data(), nE * 4);
-    return true;
-}
-
-// RWT2 table (k_traverse_rows): one u32 ENTRY per child of every internal
-// node that is not a leaf parent ("LP" nodes, whose labels are base column +
-// bit, or entry bit of a column list: no entries, no frame), u32 words
-//   [0] the root's entry, [1] nE, [2] frames (non-LP internal levels on a
-//   path), [3] 0 (or the path table's offset, append_path_table), nE
-//   entries, then the column lists (u16) of the leaf parents whose columns
-//   are not consecutive (the greedy partitioner's groups); an entry is
-//     leaf      0x80000000 | column
-//     LP node   0xC0000000 | arity << 16 | first column
-//     LP list   0xE0000000 | arity << 16 | first u16 of its column list
-//     internal  arity << 16 | first entry of its children
-// so the walk reads ONE table word per visited child.
-bool build_rwt2_table(const Tree &tree, std::vector<uint32_t> &t2, uint32_t &frames, std::vector<uint32_t> *slot_dnode) {
-    t2.clear();
-    frames = 0;
-    const auto &N = tree.nodes;
-    if (N.size() < 2) return false;
-    const bool folded = tree.folded;
-    const uint32_t root = folded ? 0u : 1u;
-    if (N[root].kind == KIND_LEAF || N[root].arity == 0) return false;
-    auto column_of = [&](const DevNode &d) { return tree.label_perm.empty() ? d.label : tree.label_perm[d.label]; };
-    // a leaf parent: base = its first column (consecutive: cons) 
-    auto is_lp2 = [&](uint32_t v, uint32_t &base, bool &cons) {
-        const DevNode &d = N[v];
-        cons = true;
-        for (uint32_t c = 0; c < d.arity; ++c) {
-            const DevNode &w = N[d.first_child + c];
-            if (w.kind != KIND_LEAF) return false;
-            if (c == 0) base = column_of(w);
-            else if (column_of(w) != base + c) cons = false;
-        }
-        return d.arity > 0;
-    };
-    auto is_lp = [&](uint32_t v, uint32_t &base) {
-        bool cons;
-        return is_lp2(v, base, cons);
-    };
-    std::vector<uint16_t> lists;  // the column lists of non-consecutive leaf parents
-    // non-LP internal nodes in BFS order, each with its first entry
-    std::vector<uint32_t> order{root}, depth{1}, first;
-    uint32_t nE = 0;
-    std::vector<uint32_t> first_of(N.size(), 0);
-    uint32_t rb = 0;
-    bool root_cons = false;
-    const bool root_lp = is_lp2(root, rb, root_cons) && root_cons;  // (a listed root: an internal node)
-    if (!root_lp) {
-        for (size_t h = 0; h < order.size(); ++h) {
-            const uint32_t v = order[h];
-            const DevNode &d = N[v];
-            if (d.arity == 0 || d.arity > kRowsMaxArity) return false;
-            frames = std::max(frames, depth[h]);
-            first_of[v] = nE;
-            nE += d.arity;
-            for (uint32_t c = 0; c < d.arity; ++c) {
-                const uint32_t w = d.first_child + c;
-                uint32_t b;
-                if (N[w].kind == KIND_LEAF || is_lp(w, b)) continue;
-                order.push_back(w);
-                depth.push_back(depth[h] + 1);
-            }
-        }
-    } else if (N[root].arity > kRowsMaxArity) {
-        return false;
-    }
-    if (nE >= 0x10000 || 4 + (size_t)nE > kRowsMaxTableWords) return false;
-    auto entry = [&](uint32_t w, uint32_t &out) -> bool {
-        const DevNode &d = N[w];
-        if (d.kind == KIND_LEAF) {
-            const uint32_t col = column_of(d);
-            if (col >= 0x10000) return false;
-            out = 0x80000000u | col;
-            return true;
-        }
-        if (d.arity == 0 || d.arity > kRowsMaxArity) return false;
-        uint32_t b;
-        bool cons;
-        if (is_lp2(w, b, cons)) {
-            if (cons) {
-                if (b + d.arity > 0x10000) return false;
-                out = 0xC0000000u | ((uint32_t)d.arity << 16) | b;
-                return true;
-            }
-            if (lists.size() + d.arity > 0x10000) return false;
-            out = 0xE0000000u | ((uint32_t)d.arity << 16) | (uint32_t)lists.size();
-            for (uint32_t c = 0; c < d.arity; ++c) {
-                const uint32_t col = column_of(N[d.first_child + c]);
-                if (col >= 0x10000) return false;
-                lists.push_back((uint16_t)col);
-            }
-            return true;
-        }
-        out = ((uint32_t)d.arity << 16) | first_of[w];
-        return true;
-    };
-    t2.assign(4 + nE, 0);
-    if (slot_dnode) {  // (terminal records: the dnode of every entry; slot nE = the root)
-        slot_dnode->assign(nE + 1, ~0u);
-        (*slot_dnode)[nE] = root;
-        if (!root_lp)
-            for (const uint32_t v : order)
-                for (uint32_t c = 0; c < N[v].arity; ++c) (*slot_dnode)[first_of[v] + c] = N[v].first_child + c;
-    }
-    if (!entry(root, t2[0])) return false;
-    t2[1] = nE;
-    t2[2] = frames;
-    if (!root_lp)
-        for (const uint32_t v : order) {
-            const DevNode &d = N[v];
-            for (uint32_t c = 0; c < d.arity; ++c)
-                if (!entry(d.first_child + c, t2[4 + first_of[v] + c])) return false;
-        }
-    for (size_t i = 0; i < lists.size(); i += 2)
-        t2.push_back((uint32_t)lists[i] | (i + 1 < lists.size() ? (uint32_t)lists[i + 1] << 16 : 0u));
-    return t2.size() <= kRowsMaxTableWords;
-}
-
-// K when every root-to-leaf path of the RWT2 table crosses exactly K internal
-// entries (the root included) and then a leaf parent (rows_walk_uni), else 0
-uint32_t rwt2_uniform_levels(const std::vector<uint32_t> &t2) {
-    if (t2.size() < 4 || (t2[0] >> 30) != 0u) return 0;  // the root is a leaf parent (or a leaf)
-    const uint32_t K = t2[2];
-    if (K < 1 || K > 5) return 0;
-    std::vector<uint32_t> lev{t2[0]};
-    for (uint32_t d = 1; d <= K; ++d) {
-        std::vector<uint32_t> next;
-        for (const uint32_t w : lev) {
-            const uint32_t a = (w >> 16) & 0x7Fu, f = w & 0xFFFFu;
-            for (uint32_t c = 0; c < a; ++c) {
-                if (4 + (size_t)f + c >= t2.size()) return 0;
-                const uint32_t e = t2[4 + f + c];
-                if ((e >> 29) != (d == K ? 6u : 0u)) return 0;  // consecutive leaf parents exactly at depth K + 1
-                if (d < K) next.push_back(e);
-            }
-        }
-        lev.swap(next);
-    }
-    return K;
-}
-
-// The PATH TABLE of a uniform tree (rows_walk_path): every leaf parent's
-// first column indexed by the child indices on its path from the root,
-// idx = ((c_0 A_1 + c_1) A_2 + ...) A_{K-1} + c_{K-1}, A_k = the largest
-// arity at level k (level 0 = the root).  Appended to the RWT2 table: t2[3]
-// = its word offset, word 0 = A_1..A_{K-1} (4 bits each), then the u16
-// columns.  The odometer then never reads the table to follow a level: it
-// keeps the path index, and the leaf parent's column is one LDS read.
-// Empty (t2[3] = 0) when the table would exceed kRowsMaxPathEntries.
-constexpr uint32_t kRowsMaxPathEntries = 4096;
-void append_path_table(std::vector<uint32_t> &t2, uint32_t K) {
-    if (!K || t2.size() < 4) return;
-    std::vector<uint32_t> A(K, 0);
-    std::vector<uint32_t> lev{t2[0]};
-    for (uint32_t d = 0; d < K; ++d) {  // A[d] = the largest arity at level d
-        std::vector<uint32_t> next;
-        for (const uint32_t w : lev) {
-            const uint32_t a = (w >> 16) & 0x7Fu, f = w & 0xFFFFu;
-            A[d] = std::max(A[d], a);
-            if (d + 1 < K)
-                for (uint32_t c = 0; c < a; ++c) next.push_back(t2[4 + f + c]);
-        }
-        lev.swap(next);
-    }
-    uint64_t entries = 1;
-    for (uint32_t d = 0; d < K; ++d) entries *= A[d];
-    if (entries > kRowsMaxPathEntries || entries == 0) return;
-    std::vector<uint16_t> col(entries, 0);
-    std::vector<uint8_t> set(entries, 0);
-    // depth-first over the paths
-    struct F {
-        uint32_t w, idx, d;
-    };
-    std::vector<F> st{{t2[0], 0, 0}};
-    while (!st.empty()) {
-        const F fr = st.back();
-        st.pop_back();
-        const uint32_t a = (fr.w >> 16) & 0x7Fu, f = fr.w & 0xFFFFu;
-        for (uint32_t c = 0; c < a; ++c) {
-            const uint32_t e = t2[4 + f + c];
-            const uint32_t idx = fr.idx * A[fr.d] + c;
-            if (fr.d + 1 == K) {  // a leaf parent: its first column
-                col[idx] = (uint16_t)(e & 0xFFFFu);
-                set[idx] = 1;
-            }
-            else st.push_back(F{e, idx, fr.d + 1});
-        }
-    }
-    uint32_t packed = 0;
-    for (uint32_t d = 1; d < K; ++d) packed |= A[d] << (4 * (d - 1));
-    // a LINEAR path table (every leaf parent's first column = its path index
-    // << s: the basic partitioner's trees, whose only incomplete nodes are the
-    // last of their level -- C2-C4 with s = 3) is flagged in bit 31, s in bits
-    // 24..28: the walk then computes the column instead of reading it
-    for (uint32_t sh = 0; sh < 16; ++sh) {
-        bool lin = true;
-        for (uint64_t i = 0; i < entries && lin; ++i) lin = !set[i] || col[i] == (uint32_t)(i << sh);
-        if (lin) {
-            packed |= 0x80000000u | sh << 24;
-            break;
-        }
-    }
-    t2[3] = (uint32_t)t2.size();
-    t2.push_back(packed);
-    for (size_t i = 0; i < col.size(); i += 2)
-        t2.push_back((uint32_t)col[i] | (i + 1 < col.size() ? (uint32_t)col[i + 1] << 16 : 0u));
-}
-
-// TERMINAL records (r06, MBRWT_BUILD_ROWS_CODE = 2; rows_record.hpp
-// term_walk): every RWT2 entry that is a leaf or a leaf parent is a
-// terminal.  TT = [w | ib << 8, nT, 0, 0, nT entry words, the RWT2 column
-// lists]; the build table BT = [root entry, the root's terminal id (a
-// one-level tree), nE, 0, nE entries, nE terminal ids (internal: ~0)] for
-// the build's walk.  False when the fields would not fit 28 bits (more than
-// 4,096 terminals or a leaf parent wider than 16).
-bool build_term_tables(const std::vector<uint32_t> &t2, std::vector<uint32_t> &tt, std::vector<uint32_t> &bt,
-                       std::vector<uint32_t> &term_slot) {
-    tt.clear();
-    bt.clear();
-    term_slot.clear();
-    if (t2.size() < 4) return false;
-    const uint32_t root = t2[0], nE = t2[1];
-    const size_t lists_end = t2[3] ? (size_t)t2[3] : t2.size();
-    if (4 + (size_t)nE > lists_end) return false;
-    std::vector<uint32_t> ent, tid(nE, ~0u);
-    uint32_t mbits = 0;
-    auto is_term = [](uint32_t e) { return (e >> 31) != 0u; };
-    auto lp_arity = [](uint32_t e) { return (e >> 30) == 3u ? (e >> 16) & 0x7Fu : 0u; };
-    if ((root >> 30) == 3u) {  // a one-level tree: the root is the only terminal
-        ent.push_back(root);
-        term_slot.push_back(nE);
-        mbits = lp_arity(root);
-    } else {
-        for (uint32_t i = 0; i < nE; ++i) {
-            const uint32_t e = t2[4 + i];
-            if (!is_term(e)) continue;
-            tid[i] = (uint32_t)ent.size();
-            ent.push_back(e);
-            term_slot.push_back(i);
-            mbits = std::max(mbits, lp_arity(e));
-        }
-    }
-    const uint32_t nT = (uint32_t)ent.size();
-    uint32_t ib = 1;
-    while ((1u << ib) < nT) ++ib;
-    if (nT == 0 || nT > 4096 || mbits > 16 || ib + mbits > 28) return false;
-    const uint32_t w = ib + mbits;
-    tt = {w | ib << 8, nT, 0u, 0u};
-    tt.insert(tt.end(), ent.begin(), ent.end());
-    tt.insert(tt.end(), t2.begin() + 4 + nE, t2.begin() + lists_end);
-    bt = {root, 0u, nE, 0u};
-    bt.insert(bt.end(), t2.begin() + 4, t2.begin() + 4 + nE);
-    bt.insert(bt.end(), tid.begin(), tid.end());
-    return tt.size() <= kRowsMaxTableWords;
-}
-
-// WT (terminal records' V accounting): every terminal's chain of ancestor
-// dnodes from the root down, their arities, the chain's length and the
-// terminal's own arity (a leaf parent's; 0 for a leaf).  The parents come
-// from the logical tree below the root (as build_rwt_table walks it).
-bool build_work_table(const Tree &tree, const std::vector<uint32_t> &term_dnode, std::vector<uint32_t> &wt) {
-    const auto &N = tree.nodes;
-    const uint32_t root = tree.folded ? 0u : 1u;
-    std::vector<uint32_t> parent(N.size(), ~0u), q{root};
-    for (size_t h = 0; h < q.size(); ++h) {
-        const DevNode &v = N[q[h]];
-        if (v.kind == KIND_LEAF) continue;
-        for (uint32_t c = 0; c < v.arity; ++c) {
-            const uint32_t w = v.first_child + c;
-            if (w >= N.size()) return false;
-            parent[w] = q[h];
-            if (N[w].kind != KIND_LEAF) q.push_back(w);
-        }
-    }
-    const uint32_t nT = (uint32_t)term_dnode.size();
-    std::vector<std::vector<uint32_t>> chains(nT);
-    uint32_t D = 1;
-    for (uint32_t t = 0; t < nT; ++t) {
-        const uint32_t u = term_dnode[t];
-        if (u >= N.size()) return false;
-        for (uint32_t a = u == root ? ~0u : parent[u]; a != ~0u; a = a == root ? ~0u : parent[a]) {
-            chains[t].push_back(a);
-            if (chains[t].size() > 32) return false;
-        }
-        std::reverse(chains[t].begin(), chains[t].end());
-        D = std::max<uint32_t>(D, (uint32_t)chains[t].size());
-    }
-    wt.assign(4 + (size_t)nT * (2 * D + 2), 0u);
-    wt[0] = D;
-    wt[1] = nT;
-    for (uint32_t t = 0; t < nT; ++t) {
-        const uint32_t u = term_dnode[t];
-        for (uint32_t k = 0; k < chains[t].size(); ++k) {
-            wt[4 + (size_t)t * D + k] = chains[t][k];
-            wt[4 + (size_t)nT * D + (size_t)t * D + k] = N[chains[t][k]].arity;
-        }
-        wt[4 + (size_t)2 * nT * D + t] = (uint32_t)chains[t].size();
-        wt[4 + (size_t)2 * nT * D + nT + t] = N[u].kind == KIND_LEAF ? 0u : N[u].arity;
-    }
-    return true;
-}
-
-namespace {
-
-// the terminals of row r's descent in pre-order, term(id, children mask):
-// the row's masks (emit_row_masks) walked over the build table BT
-// (build_term_tables).  False when the row has more than kTermMaxMasks masks
-// or its masks do not follow the table.
-constexpr uint32_t kTermMaxMasks = 256;
-template <class Term>
-__device__ bool row_terms(const DevNode *nodes, bool folded, uint32_t r, const uint32_t *bt, Term term,
-                          uint32_t &labels) {
-    uint16_t mb[kTermMaxMasks];
-    uint32_t nm = 0;
-    labels = emit_row_masks(nodes, folded, r, [&](uint64_t mk, uint32_t, uint32_t) {
-        if (nm < kTermMaxMasks) mb[nm] = (uint16_t)mk;
-        ++nm;
-    });
-    if (labels == ~0u || nm > kTermMaxMasks) return false;
-    if (!nm) return labels == 0;
-    const uint32_t root = gld(bt);
-    if ((root >> 30) == 3u) {  // a one-level tree
-        term(gld(bt + 1), (uint32_t)mb[0]);
-        return nm == 1;
-    }
-    const uint32_t nE = gld(bt + 2);
-    const uint32_t *ent = bt + 4, *tid = bt + 4 + nE;
-    uint32_t pos = 1, m = mb[0], f = root & 0xFFFFu;
-    uint32_t sf[kRowsMaxHeight], sm[kRowsMaxHeight];
-    int sp = 0;
-    while (true) {
-        if (!m) {
-            if (!sp) break;
-            --sp;
-            f = sf[sp];
-            m = sm[sp];
-            continue;
-        }
-        const uint32_t c = (uint32_t)__builtin_ctz(m);
-        m &= m - 1u;
-        const uint32_t sl = f + c;
-        if (sl >= nE) return false;
-        const uint32_t e = gld(ent + sl);
-        if ((e >> 31) == 0u) {  // an internal node: its mask, one level down
-            if (pos >= nm || (m && sp == (int)kRowsMaxHeight)) return false;
-            if (m) {
-                sf[sp] = f;
-                sm[sp] = m;
-                ++sp;
-            }
-            f = e & 0xFFFFu;
-            m = mb[pos++];
-        } else if ((e >> 30) == 3u) {  // a leaf parent: a terminal with its mask
-            if (pos >= nm) return false;
-            term(gld(tid + sl), (uint32_t)mb[pos++]);
-        } else {  // a leaf: a terminal of its own
-            term(gld(tid + sl), 0u);
-        }
-    }
-    return pos == nm;
-}
-// row r's terminal fields (w bits: id | mask << ib) from byte p on; the
-// bytes written, or ~0u
-__device__ __forceinline__ uint32_t write_row_terms(const DevNode *nodes, bool folded, uint32_t r, uint8_t *p,
-                                                    const uint32_t *bt, uint32_t w, uint32_t ib, uint32_t &labels) {
-    uint64_t acc = 0;
-    uint32_t nb = 0, wr = 0;
-    const bool ok = row_terms(
-        nodes, folded, r, bt,
-        [&](uint32_t id, uint32_t m) {
-            acc |= (uint64_t)(id | (m << ib)) << nb;
-            nb += w;
-            while (nb >= 8u) {
-                p[wr++] = (uint8_t)acc;
-                acc >>= 8;
-                nb -= 8u;
-            }
-        },
-        labels);
-    if (nb) p[wr++] = (uint8_t)acc;
-    return ok ? wr : ~0u;
-}
-
-// per row of a range: record size (1 + mask bytes, < 2^15) | 0x8000 when the
-// row has >= 255 labels (its count does not fit the inline byte)
-// (nib: the masks as nibble codes, rows_record.hpp RecMasks)
-__global__ __launch_bounds__(256) void k_rows_measure(const DevNode *nodes, uint32_t folded, uint64_t n, uint16_t *sz,
-                                                      unsigned long long *acc, uint32_t code, const uint32_t *bt,
-                                                      uint32_t w) {
-    const bool nib = code == 1u;
-    unsigned long long lab = 0, bytes = 0, bad = 0, bytes1 = 0;
-    const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gs) {
-        uint32_t b = 1, nn = 0, b1 = 1;
-        uint32_t L = emit_row_masks(nodes, folded != 0, (uint32_t)r, [&](uint64_t mk, uint32_t a, uint32_t) {
-            if (nib) nn += nib_codes((uint32_t)mk);
-            else b += rec_mask_bytes(a);
-            b1 += rec_mask_bytes(a);
-        });
-        b += (nn + 1) / 2;
-        if (code == 2u && L != ~0u) {  // terminal records: the fields' bytes
-            uint32_t nt = 0, L2 = 0;
-            b = row_terms(nodes, folded != 0, (uint32_t)r, bt, [&](uint32_t, uint32_t) { ++nt; }, L2) && L2 == L
-                    ? 1u + (nt * w + 7u) / 8u
-                    : 0x8000u;  // (a row the fields cannot hold: bad)
-        }
-        bytes1 += b1;
-        // (a row of >= 2^15 labels: the temp regions carry a row's count in
-        // 15 bits beside the long-record flag, k_traverse_rows / k_compact_tiles)
-        if (L == ~0u || b >= 0x8000 || L > 0x7FFFu) {
-            ++bad;
-            sz[r] = 0x7FFF;
-            continue;
-        }
-        sz[r] = (uint16_t)(b | (L >= 255 ? 0x8000u : 0u));
-        lab += L;
-        bytes += b;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        lab += __shfl_down(lab, off);
-        bytes += __shfl_down(bytes, off);
-        bad += __shfl_down(bad, off);
-        bytes1 += __shfl_down(bytes1, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (lab) atomicAdd(acc + 0, lab);
-        if (bytes) atomicAdd(acc + 1, bytes);
-        if (bad) atomicAdd(acc + 2, bad);
-        if (bytes1) atomicAdd(acc + 3, bytes1);  // (the byte-coded size, beside a nibble measure)
-    }
-}
-
-// which rows of a block spill: rows with >= 255 labels always; then, while
-// the block overflows, the largest inline record (a spilled entry takes 5
-// bytes in the block)
-__device__ __forceinline__ uint32_t block_spills(const uint32_t *s, uint32_t nrows, uint32_t S, uint32_t B) {
-    uint32_t used = S, spilled = 0;
-    for (uint32_t t = 0; t < nrows; ++t) {
-        if (s[t] & 0x8000u) {
-            spilled |= 1u << t;
-            used += 5;
-        } else {
-            used += s[t];
-        }
-    }
-    while (used > B) {
-        uint32_t best = 0, bt = 0;
-        for (uint32_t t = 0; t < nrows; ++t)
-            if (!((spilled >> t) & 1u) && s[t] >= best) {
-                best = s[t];
-                bt = t;
-            }
-        spilled |= 1u << bt;
-        used = used - best + 5;
-    }
-    return spilled;
-}
-__device__ __forceinline__ uint32_t spill_units(uint32_t s) { return (8 + ((s & 0x7FFFu) - 1) + 15) / 16; }
-
-// a candidate (B, S): spilled rows, spill units, rows whose spill entry is
-// longer than a block (direct pass)
-__global__ __launch_bounds__(256) void k_rows_plan(const uint16_t *sz, uint64_t n, uint32_t B, uint32_t S,
-                                                   unsigned long long *acc) {
-    unsigned long long sp = 0, units = 0, lng = 0;
-    const uint64_t nb = (n + S - 1) / S;
-    const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < nb; b += gs) {
-        uint32_t s[16];
-        const uint32_t nr = (uint32_t)std::min<uint64_t>(S, n - b * S);
-        for (uint32_t t = 0; t < nr; ++t) s[t] = gld(sz + b * S + t);
-        const uint32_t m = block_spills(s, nr, S, B);
-        for (uint32_t t = 0; t < nr; ++t)
-            if ((m >> t) & 1u) {
-                ++sp;
-                units += spill_units(s[t]);
-                lng += (8 + (s[t] & 0x7FFFu) - 1 > B) ? 1u : 0u;
-            }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        sp += __shfl_down(sp, off);
-        units += __shfl_down(units, off);
-        lng += __shfl_down(lng, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (sp) atomicAdd(acc + 0, sp);
-        if (units) atomicAdd(acc + 1, units);
-        if (lng) atomicAdd(acc + 2, lng);
-    }
-}
-
-// the masks of row r written from byte p on (bytes, or nibble codes); the
-// bytes written
-__device__ __forceinline__ uint32_t write_row_masks(const DevNode *nodes, bool folded, uint32_t r, uint8_t *p,
-                                                    uint32_t nib, uint32_t &labels) {
-    uint32_t w = 0;
-    auto put = [&](uint32_t v) {  // nibble w: byte w / 2, low half first
-        if (w & 1u) p[w >> 1] |= (uint8_t)(v << 4);
-        else p[w >> 1] = (uint8_t)v;
-        ++w;
-    };
-    labels = emit_row_masks(nodes, folded, r, [&](uint64_t mk, uint32_t a, uint32_t) {
-        if (nib) {  // (arity <= 8)
-            if (nib_codes((uint32_t)mk) == 1u) {
-                put((uint32_t)__builtin_ctzll(mk));
-            } else {
-                put(8u);
-                put((uint32_t)mk & 15u);
-                put((uint32_t)(mk >> 4) & 15u);
-            }
-        } else {  // one byte per 8 children, little-endian
-            for (uint32_t k = 0; k < a; k += 8) p[w++] = (uint8_t)(mk >> k);
-        }
-    });
-    return nib ? (w + 1) / 2 : w;
-}
-
-// one thread per block of the range: header, inline records, spill entries
-__global__ __launch_bounds__(256) void k_rows_write(const DevNode *nodes, uint32_t folded, uint64_t nr_range,
-                                                    const uint16_t *sz, uint32_t B, uint32_t S, uint8_t *blocks,
-                                                    uint8_t *spill, unsigned long long *spill_used, uint32_t code,
-                                                    const uint32_t *bt, uint32_t w, uint32_t ib) {
-    const uint32_t nib = code == 1u ? 1u : 0u;
-    auto write = [&](uint32_t r, uint8_t *p, uint32_t &L) -> uint32_t {
-        return code == 2u ? write_row_terms(nodes, folded != 0, r, p, bt, w, ib, L)
-                          : write_row_masks(nodes, folded != 0, r, p, nib, L);
-    };
-    const uint64_t nb = (nr_range + S - 1) / S;
-    const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < nb; b += gs) {
-        uint32_t s[16];
-        const uint32_t nr = (uint32_t)std::min<uint64_t>(S, nr_range - b * S);
-        for (uint32_t t = 0; t < nr; ++t) s[t] = gld(sz + b * S + t);
-        const uint32_t m = block_spills(s, nr, S, B);
-        uint8_t *blk = blocks + b * B;
-        uint32_t o = S;
-        for (uint32_t t = 0; t < nr; ++t) {
-            const uint32_t r = (uint32_t)(b * S + t);
-            if ((m >> t) & 1u) {
-                const uint64_t idx = atomicAdd(spill_used, (unsigned long long)spill_units(s[t]));
-                uint8_t *se = spill + idx * 16;
-                uint32_t L = 0;
-                const uint32_t nw = write(r, se + 8, L);
-                *reinterpret_cast<uint32_t *>(se) = L;
-                *reinterpret_cast<uint32_t *>(se + 4) = nw;
-                blk[t] = (uint8_t)(o | 0x80u);
-                blk[o] = (uint8_t)std::min<uint32_t>(L, 255);
-                for (uint32_t k = 0; k < 4; ++k) blk[o + 1 + k] = (uint8_t)(idx >> (8 * k));
-                o += 5;
-            } else {
-                blk[t] = (uint8_t)o;
-                uint32_t L = 0;
-                const uint32_t nw = write(r, blk + o + 1, L);
-                blk[o] = (uint8_t)L;
-                o += 1 + nw;
-            }
-        }
-    }
-}
-
-}  // namespace
-
-// ------------------------------------------------------------------------
-// build driver
-// ------------------------------------------------------------------------
-// The layout of the whole image, chosen on the first range (choose_layout);
-// every later range is written under it.
-struct RowsPlan {
-    bool var = false;              // variable-length records (rows_var.hip) instead of blocks
-    BlockShape block{0, 0};        // blocks: their bytes and rows per block
-    double var_bytes_per_row = 0;  // variable-length records: their size per row on the first range
-};
-
-struct RowsBuild {
-    Ctx *top = nullptr;
-    uint64_t n = 0, align = 1;
-    std::optional<RowsPlan> plan;  // unset until the first range has decided (record code: img.term / img.nib)
-    bool auto_layout = false;  // layout AUTO: decline records that cost more than kAutoMaxCost requests per row
-    int footprint = 0;         // MBRWT_BUILD_ROWS_FOOTPRINT of the creating thread
-    VarScratch vws;            // variable-length records (rows_var.hip)
-    RowsImage img;
-    unsigned long long *d_acc = nullptr;  // [0..3] measure, [4..7] plan
-    uint16_t *d_sz = nullptr;
-    uint64_t sz_cap = 0;
-    hipStream_t s = nullptr;
-    uint32_t *d_bt = nullptr;  // terminal records: the build table (build_term_tables)
-
-    RowsBuild() = default;
-    RowsBuild(const RowsBuild &) = delete;
-    RowsBuild &operator=(const RowsBuild &) = delete;
-    ~RowsBuild();  // the one release: scratch, and the image unless rows_build_finish moved it out
-};
-
-void free_rows(RowsImage &r) {
-    for (void *p : r.var_chunks) (void)hipFree(p);
-    if (r.var_lines) (void)hipFree(r.var_lines);
-    if (r.d_var_units) (void)hipFree(r.d_var_units);
-    if (r.d_var_anc) (void)hipFree(r.d_var_anc);
-    if (r.d_unit_of) (void)hipFree(r.d_unit_of);
-    if (r.blocks) (void)hipFree(r.blocks);
-    if (r.spill) (void)hipFree(r.spill);
-    if (r.d_spill_used) (void)hipFree(r.d_spill_used);
-    if (r.d_table) (void)hipFree(r.d_table);
-    if (r.d_table2) (void)hipFree(r.d_table2);
-    if (r.d_table3) (void)hipFree(r.d_table3);
-    if (r.d_table4) (void)hipFree(r.d_table4);
-    if (r.classes) (void)hipFree(r.classes);
-    r = RowsImage();
-}
-
-RowsBuild *rows_build_begin(Ctx &top, uint64_t num_rows, uint64_t align, bool auto_layout) {
-    RowsBuild *rb = new (std::nothrow) RowsBuild();
-    if (!rb) return nullptr;
-    rb->top = &top;
-    rb->auto_layout = auto_layout;
-    rb->footprint = g_rows_footprint;
-    rb->n = num_rows;
-    rb->align = std::max<uint64_t>(1, align);
-    rb->s = top.stream;
-    if (hipMalloc(&rb->d_acc, 8 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc(&rb->img.d_spill_used, sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(rb->img.d_spill_used, 0, sizeof(unsigned long long)) != hipSuccess) {
-        rows_build_abort(rb);
-        return nullptr;
-    }
-    return rb;
-}
-
-RowsBuild::~RowsBuild() {
-    if (d_acc) (void)hipFree(d_acc);
-    if (d_sz) (void)hipFree(d_sz);
-    if (d_bt) (void)hipFree(d_bt);
-    var_free_scratch(vws);
-    free_rows(img);
-}
-
-void rows_build_abort(RowsBuild *rb) { delete rb; }
-
-static int read_acc(RowsBuild &rb, unsigned long long *h, int k) {
-    MBRWT_HIP(hipMemcpyAsync(h, rb.d_acc, k * sizeof(unsigned long long), hipMemcpyDeviceToHost, rb.s));
-    MBRWT_HIP(hipStreamSynchronize(rb.s));
-    return MBRWT_OK;
-}
-
-// grow the spill area to hold `bytes` (entries keep their offsets: copy)
-static int ensure_spill(RowsBuild &rb, uint64_t bytes) {
-    RowsImage &im = rb.img;
-    const uint64_t need = bytes + im.B + 256;
-    if (need <= im.spill_cap) return MBRWT_OK;
-    const uint64_t cap = std::max<uint64_t>(need, im.spill_cap + im.spill_cap / 4);
-    uint8_t *p = nullptr;
-    MBRWT_HIP(hipMalloc(&p, cap));
-    MBRWT_HIP(hipMemsetAsync(p, 0, cap, rb.s));
-    if (im.spill) {
-        MBRWT_HIP(hipMemcpyAsync(p, im.spill, im.spill_cap, hipMemcpyDeviceToDevice, rb.s));
-        MBRWT_HIP(hipStreamSynchronize(rb.s));
-        MBRWT_HIP(hipFree(im.spill));
-    }
-    im.spill = p;
-    im.spill_cap = cap;
-    return MBRWT_OK;
-}
-
-// the record code the image stands at: prepare_tables' candidate, settled by
-// choose_code on the first range (0 byte masks, 1 nibble codes, 2 terminal
-// records), and the terminal fields' widths (word 0 of the TT table)
-static uint32_t record_code(const RowsImage &im) { return im.term ? 2u : im.nib ? 1u : 0u; }
-static uint32_t term_width(const RowsImage &im) { return im.term ? im.table3[0] & 0xFFu : 0u; }
-static uint32_t term_id_bits(const RowsImage &im) { return im.term ? (im.table3[0] >> 8) & 0xFFu : 0u; }
-
-// Prepare, once: the RWT / RWT2 / path tables of the tree's shape and, where
-// the build options and the shape allow them, the nibble codes or the
-// terminal records' tables (TT, work table, the build table on the device).
-// Leaves the candidate record code in im.nib / im.term.
-static int prepare_tables(RowsBuild &rb, Ctx &range) {
-    RowsImage &im = rb.img;
-    if (!build_rwt_table(range.tree, im.table, im.height, im.max_arity) ||
-        !build_rwt2_table(range.tree, im.table2, im.frames, &im.slot_dnode)) {
-        im.table.clear();
-        set_error("tree shape outside the row-record limits (arity <= 64, columns < 2^16, height <= 16, a walk table of <= 8192 words)");
-        return MBRWT_ERR_UNSUPPORTED;
-    }
-    // one-byte masks everywhere (rows_walk6): the root and every internal
-    // or leaf-parent entry of arity <= 8
-    auto ar8 = [](uint32_t e) { return (e >> 30) == 2u || ((e >> 16) & 0x7Fu) <= 8; };
-    im.mask1 = ar8(im.table2[0]);
-    for (size_t i = 4; i < 4 + (size_t)im.table2[1]; ++i) im.mask1 = im.mask1 && ar8(im.table2[i]);
-    im.uni = im.mask1 ? rwt2_uniform_levels(im.table2) : 0u;
-    if (im.uni) append_path_table(im.table2, im.uni);
-    // masks wider than 16 bits (r06: arity up to 64) are read by the tree
-    // odometer and the one-lane walks only: such a tree needs the tree
-    // odometer's depth
-    // (im.max_arity: over the nodes the walk reaches -- record-only
-    // dnodes such as PACKT_IN carry other arities)
-    if (im.max_arity > 16 && im.frames > kRowsOdoLevels) {
-        im.table.clear();
-        set_error("row records: a node wider than 16 children in a tree deeper than the tree odometer (8 levels)");
-        return MBRWT_ERR_UNSUPPORTED;
-    }
-    // nibble-coded masks (MBRWT_BUILD_ROWS_CODE = 1, r06): read by the
-    // path-table odometer and the one-lane walks, so uniform trees of
-    // one-byte masks with a path table only (the others keep bytes)
-    im.nib = build_tuning().rows_code == 1 && im.uni && im.table2.size() > 3 && im.table2[3] != 0;
-    // terminal records (r06; MBRWT_BUILD_ROWS_CODE 0 = AUTO, the default,
-    // or 2): trees of masks up to 16 bits whose terminals fit the fields
-    im.term = false;
-    // (AUTO, code 0: where they are smaller than byte masks -- decided on
-    // the first range by choose_code; code 3 forces byte masks)
-    const int code = build_tuning().rows_code;
-    if ((code == 0 || code == 2) && im.max_arity <= 16) {
-        std::vector<uint32_t> bt, term_slot;
-        bool ok = build_term_tables(im.table2, im.table3, bt, term_slot);
-        if (ok) {
-            im.term_dnode.resize(term_slot.size());
-            for (size_t i = 0; i < term_slot.size(); ++i)
-                im.term_dnode[i] = term_slot[i] < im.slot_dnode.size() ? im.slot_dnode[term_slot[i]] : ~0u;
-            ok = build_work_table(range.tree, im.term_dnode, im.table4);
-        }
-        if (ok) {
-            if (!rb.d_bt) {
-                if (hipMalloc(&rb.d_bt, bt.size() * 4) != hipSuccess) return hip_fail(hipGetLastError(), "build table");
-                MBRWT_HIP(hipMemcpy(rb.d_bt, bt.data(), bt.size() * 4, hipMemcpyHostToDevice));
-            }
-            im.term = true;
-        }
-    }
-    return MBRWT_OK;
-}
-
-// k_rows_measure's counters of one range
-struct Measure {
-    unsigned long long labels, bytes, bad, byte_coded;  // (bad: rows the code cannot hold)
-};
-
-// Measure, per range: every row's record size under the image's record code
-// (into d_sz) and the range's counters
-static int measure_range(RowsBuild &rb, Ctx &range, Measure &h) {
-    const RowsImage &im = rb.img;
-    const uint64_t nr = range.tree.num_rows;
-    MBRWT_HIP(hipMemsetAsync(rb.d_acc, 0, 8 * sizeof(unsigned long long), rb.s));
-    hipLaunchKernelGGL(k_rows_measure, dim3(grid256(nr)), dim3(256), 0, rb.s, range.d_nodes,
-                       range.tree.folded ? 1u : 0u, nr, rb.d_sz, rb.d_acc, record_code(im), (const uint32_t *)rb.d_bt,
-                       term_width(im));
-    MBRWT_HIP(hipGetLastError());
-    unsigned long long a[4];
-    if (int rc = read_acc(rb, a, 4)) return rc;
-    h = Measure{a[0], a[1], a[2], a[3]};
-    return MBRWT_OK;
-}
-
-// Decide, on the first range: the record code of the whole image (the rule:
-// rows_plan.hpp); a code that gives way is measured again as what follows it
-static int choose_code(RowsBuild &rb, Ctx &range, Measure &h) {
-    RowsImage &im = rb.img;
-    if (im.term && term_gives_way(h.bad, h.bytes, h.byte_coded)) {
-        im.term = false;
-        im.table3.clear();
-        if (int rc = measure_range(rb, range, h)) return rc;
-    }
-    if (im.nib && nib_gives_way(h.bad, h.bytes, h.byte_coded)) {
-        im.nib = false;
-        if (int rc = measure_range(rb, range, h)) return rc;
-    }
-    return MBRWT_OK;
-}
-
-// k_rows_plan's counters of the measured range under one block shape
-static int plan_range(RowsBuild &rb, Ctx &range, BlockShape bs, PlanCounts &out) {
-    const uint64_t nr = range.tree.num_rows;
-    MBRWT_HIP(hipMemsetAsync(rb.d_acc, 0, 8 * sizeof(unsigned long long), rb.s));
-    hipLaunchKernelGGL(k_rows_plan, dim3(grid256((nr + bs.S - 1) / bs.S)), dim3(256), 0, rb.s, rb.d_sz, nr, bs.B, bs.S,
-                       rb.d_acc);
-    MBRWT_HIP(hipGetLastError());
-    unsigned long long o[3];
-    if (int rc = read_acc(rb, o, 3)) return rc;
-    out = PlanCounts{o[0], o[1], o[2]};
-    return MBRWT_OK;
-}
-
-// the variable-length records of the first range measured: whether they
-// apply (ok), the whole image's bytes, the bytes per row into the plan
-static int measure_var(RowsBuild &rb, Ctx &range, bool forced, RowsPlan &plan, bool &ok, double &image_bytes) {
-    RowsImage &im = rb.img;
-    const uint64_t nr = range.tree.num_rows;
-    uint64_t vb = 0;
-    const int rc = var_measure_range(im, range, rb.vws, &vb, rb.s);
-    if (rc && rc != MBRWT_ERR_UNSUPPORTED) return rc;
-    ok = rc == MBRWT_OK;
-    image_bytes = var_image_bytes(vb, nr, rb.n, rb.align);
-    plan.var_bytes_per_row = (double)vb / (double)nr;
-    // a unit table so large that the decode's LDS cannot hold a mean
-    // tile beside it: AUTO keeps the other layouts (forced: allowed,
-    // every such tile then takes the decode's global path)
-    if (ok && !forced &&
-        !var_lds_fits(im, (double)range.tree.num_relations / std::max<double>(1.0, (double)range.tree.num_rows),
-                      plan.var_bytes_per_row))
-        ok = false;
-    return MBRWT_OK;
-}
-
-// the image's device memory under the plan: directory lines or blocks
-static int alloc_image(RowsBuild &rb, const RowsPlan &plan) {
-    RowsImage &im = rb.img;
-    if (plan.var) {
-        im.var = true;
-        const uint64_t nlines = (rb.n + kVarLineRows - 1) / kVarLineRows;
-        MBRWT_HIP(hipMalloc(&im.var_lines, nlines * 64));
-        MBRWT_HIP(hipMemsetAsync(im.var_lines, 0, nlines * 64, rb.s));
-        return MBRWT_OK;
-    }
-    im.B = plan.block.B;
-    im.S = plan.block.S;
-    im.magic = div_magic(im.S);
-    im.num_blocks = (rb.n + im.S - 1) / im.S;
-    MBRWT_HIP(hipMalloc(&im.blocks, im.num_blocks * im.B));
-    MBRWT_HIP(hipMemsetAsync(im.blocks, 0, im.num_blocks * im.B, rb.s));
-    return MBRWT_OK;
-}
-
-// Decide, on the first range: the layout of the whole image -- every
-// candidate (B, S) planned over the range and priced (the cost model and the
-// choice: rows_plan.hpp), the variable-length records where the blocks cost
-// too much or the build option forces them, the AUTO decline, the
-// MBRWT_BUILD_ROWS_BLOCK override -- then the image's allocation.  Sets rb.plan.
-static int choose_layout(RowsBuild &rb, Ctx &range) {
-    RowsImage &im = rb.img;
-    size_t free_b = 0, total_b = 0;
-    MBRWT_HIP(hipMemGetInfo(&free_b, &total_b));
-    const double budget = (double)free_b - 4.0 * (1ull << 30);
-    std::vector<Cand> cands;
-    for (BlockShape bs : block_candidates(rb.align)) {
-        PlanCounts o;
-        if (int rc = plan_range(rb, range, bs, o)) return rc;
-        cands.push_back(price_candidate(bs, o, range.tree.num_rows, rb.n));
-    }
-    const Choice ch = choose_block(cands, budget, cost_tolerance(rb.footprint == 1, im.uni != 0));
-    RowsPlan plan;
-    const int force_var = build_tuning().rows_var;
-    const bool want_var = force_var == 1 || ch.tmin > kAutoMaxCost;
-    bool var_ok = force_var != 0 && rb.align % kVarLineRows == 0 && var_prepare(range.tree, im);
-    // the lanes per row the decode will run with (the build option, else
-    // automatic): the LDS gate (measure_var) must judge that geometry
-    uint32_t var_G = build_tuning().var_lanes;
-    if (var_G & (var_G - 1) || var_G > 16) var_G = 0;  // (1, 2, 4, 8 or 16; 0: automatic)
-    im.var_G = var_G;
-    double var_mem = kNoFit;
-    if (var_ok && want_var)
-        if (int rc = measure_var(rb, range, force_var == 1, plan, var_ok, var_mem)) return rc;
-    if (var_ok && var_mem <= budget && want_var) {
-        plan.var = true;
-    } else {
-        if (!ch.best) {
-            set_error("row-record image does not fit the device");
-            return MBRWT_ERR_NOMEM;
-        }
-        if (rb.auto_layout && ch.tmin > kAutoMaxCost) {  // (kAutoMaxCost, rows_plan.hpp)
-            set_error("row records too long for the block layout");
-            return MBRWT_ERR_UNSUPPORTED;
-        }
-        plan.block = {ch.best->B, ch.best->S};
-        (void)block_override(build_tuning().rows_block, rb.align, plan.block);  // MBRWT_BUILD_ROWS_BLOCK
-    }
-    if (int rc = alloc_image(rb, plan)) return rc;
-    rb.plan = plan;
-    return MBRWT_OK;
-}
-
-// Write, per range: the range's records into the image under the plan --
-// blocks with their spill entries (the spill area planned and grown first),
-// or the variable-length records (rows_var.hip)
-static int write_range(RowsBuild &rb, Ctx &range, uint64_t row0) {
-    RowsImage &im = rb.img;
-    const uint64_t nr = range.tree.num_rows;
-    if (rb.plan->var) return var_build_range(im, range, row0, rb.vws, rb.s);
-    PlanCounts pc;
-    if (int rc = plan_range(rb, range, rb.plan->block, pc)) return rc;
-    unsigned long long used = 0;
-    MBRWT_HIP(hipMemcpyAsync(&used, im.d_spill_used, sizeof(used), hipMemcpyDeviceToHost, rb.s));
-    MBRWT_HIP(hipStreamSynchronize(rb.s));
-    // a spilled entry stores its offset as u32 16-byte units: the spill area
-    // addresses 64 GiB
-    if (used + pc.units >= (1ull << 32)) {
-        set_error("row-record spill area beyond 64 GiB");
-        return MBRWT_ERR_UNSUPPORTED;
-    }
-    // the first range sizes the area for the whole image (extrapolated)
-    const double scale = row0 == 0 ? (double)rb.n / (double)nr : 1.0;
-    if (int rc = ensure_spill(
-            rb, (uint64_t)(used * 16 + pc.units * 16 * scale * (row0 == 0 ? 1.05 : 1.0)) + 16 * pc.units))
-        return rc;
-    im.spilled_rows += pc.spilled;
-    im.long_rows += pc.long_rows;
-    im.spill_bytes += pc.units * 16;
-    hipLaunchKernelGGL(k_rows_write, dim3(grid256((nr + im.S - 1) / im.S)), dim3(256), 0, rb.s, range.d_nodes,
-                       range.tree.folded ? 1u : 0u, nr, rb.d_sz, im.B, im.S, im.blocks + (row0 / im.S) * im.B,
-                       im.spill, im.d_spill_used, record_code(im), (const uint32_t *)rb.d_bt, term_width(im),
-                       term_id_bits(im));
-    MBRWT_HIP(hipGetLastError());
-    MBRWT_HIP(hipStreamSynchronize(rb.s));
-    return MBRWT_OK;
-}
-
-// Records of one range: prepare (once), measure, decide (the first range, for
-// the whole image: record code, then layout), write.
-int rows_build_range(RowsBuild *rbp, Ctx &range, uint64_t row0) {
-    if (!rbp) return MBRWT_ERR_NOMEM;
-    RowsBuild &rb = *rbp;
-    RowsImage &im = rb.img;
-    const uint64_t nr = range.tree.num_rows;
-    if (!nr) return MBRWT_OK;
-    if (!range.d_nodes || range.tree.nodes.empty()) {
-        set_error("row records need a node image");
-        return MBRWT_ERR_UNSUPPORTED;
-    }
-    if (row0 % rb.align) {
-        set_error("row-record range not aligned");
-        return MBRWT_ERR_INVALID;
-    }
-    if (im.table.empty())
-        if (int rc = prepare_tables(rb, range)) return rc;
-    if (nr > rb.sz_cap) {
-        if (rb.d_sz) MBRWT_HIP(hipFree(rb.d_sz));
-        rb.d_sz = nullptr;
-        MBRWT_HIP(hipMalloc(&rb.d_sz, nr * sizeof(uint16_t)));
-        rb.sz_cap = nr;
-    }
-    Measure h;
-    if (int rc = measure_range(rb, range, h)) return rc;
-    const bool first = !rb.plan;  // the first range decides for the whole image
-    if (first)
-        if (int rc = choose_code(rb, range, h)) return rc;
-    if (h.bad) {
-        set_error("row record deeper than the build walker supports, or a row of more than 32,767 labels");
-        return MBRWT_ERR_UNSUPPORTED;
-    }
-    if (h.labels != range.tree.num_relations) {
-        set_error("row records: label count differs from the node image");
-        return MBRWT_ERR_DEVICE;
-    }
-    if (!im.var) im.record_bytes += h.bytes;
-    if (first)
-        if (int rc = choose_layout(rb, range)) return rc;
-    return write_range(rb, range, row0);
-}
-
-// device bytes the records of `rows` more rows will still allocate (the
-// variable-length records are allocated per range; blocks up front)
-uint64_t rows_build_pending_bytes(const RowsBuild *rb, uint64_t rows) {
-    return rb && rb->plan && rb->plan->var ? var_pending_bytes(rb->plan->var_bytes_per_row, rows) : 0;
-}
-
-// the finished image's tables on the device, its size, its record classes
-static int finish_image(RowsBuild &rb) {
-    RowsImage &im = rb.img;
-    if (!rb.plan) {  // no rows
-        set_error("row records of an empty matrix");
-        return MBRWT_ERR_UNSUPPORTED;
-    }
-    if (hipMalloc(&im.d_table, im.table.size() * 4) != hipSuccess ||
-        hipMemcpy(im.d_table, im.table.data(), im.table.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc(&im.d_table2, im.table2.size() * 4) != hipSuccess ||
-        hipMemcpy(im.d_table2, im.table2.data(), im.table2.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return hip_fail(hipGetLastError(), "row-record table upload");
-    if (im.term &&
-        (hipMalloc(&im.d_table3, im.table3.size() * 4) != hipSuccess ||
-         hipMemcpy(im.d_table3, im.table3.data(), im.table3.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-         hipMalloc(&im.d_table4, im.table4.size() * 4) != hipSuccess ||
-         hipMemcpy(im.d_table4, im.table4.data(), im.table4.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
-        return hip_fail(hipGetLastError(), "terminal table upload");
-    if (im.var) {
-        // (+32 zero entries: the decoder's speculative unit reads past the last word)
-        if (hipMalloc(&im.d_var_units, (im.var_units.size() + 32) * 4) != hipSuccess ||
-            hipMemset(im.d_var_units, 0, (im.var_units.size() + 32) * 4) != hipSuccess ||
-            hipMemcpy(im.d_var_units, im.var_units.data(), im.var_units.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMalloc(&im.d_var_anc, std::max<size_t>(1, im.var_anc.size()) * 4) != hipSuccess ||
-            hipMemcpy(im.d_var_anc, im.var_anc.data(), im.var_anc.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return hip_fail(hipGetLastError(), "variable-length record tables");
-        im.bytes = (rb.n + kVarLineRows - 1) / kVarLineRows * 64 + im.var_rec_bytes;
-        return MBRWT_OK;
-    }
-    if (!im.spill && ensure_spill(rb, 0)) return MBRWT_ERR_NOMEM;
-    im.bytes = im.num_blocks * im.B + im.spill_bytes;
-    // record classes where rows repeat few distinct records (rows_class.hip)
-    return rows_classes_build(im, rb.n, build_tuning().rows_classes, &im.class_sample_distinct, rb.s);
-}
-
-// uploads the tables, moves the image into the context; frees the build
-// whether it succeeds or not
-int rows_build_finish(RowsBuild *rbp) {
-    if (!rbp) return MBRWT_ERR_NOMEM;
-    std::unique_ptr<RowsBuild> rb(rbp);
-    if (int rc = finish_image(*rb)) return rc;
-    RowsImage &im = rb->img;
-    im.occ_cap = build_tuning().rows_wgs_per_cu;  // (MBRWT_BUILD_ROWS_WGS_PER_CU: occupancy sweeps)
-    im.ready = true;
-    free_rows(rb->top->rows);
-    rb->top->rows = im;
-    im = RowsImage();  // ownership moved
-    return MBRWT_OK;
-}
-
 
 // ------------------------------------------------------------------------
 // queries
@@ -1215,12 +122,6 @@ struct RowsParams {
     const uint32_t *classes;      // record classes: the packed class index (null: none; rows_class.hip)
     uint32_t class_bits;
 };
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // a u16 store at a 32-bit byte offset from a wave-uniform base (the saddr +
 // 32-bit voffset form of global_store_short: no 64-bit address arithmetic)
@@ -1923,10 +824,6 @@ struct CompactParams {
     const uint32_t *table;        // RWT (direct tiles)
     uint32_t stk_lim;             // walk stack frames (the tree's height; dynamic LDS)
 };
-__device__ __forceinline__ void publish_status(unsigned long long *status, uint64_t st) {
-    atomicMax(&status[1], (unsigned long long)st);
-    atomicOr(&status[2], 1ull << st);
-}
 template <bool WIDE>
 __global__ __launch_bounds__(256) void k_compact_tiles(CompactParams p) {
     extern __shared__ uint32_t cstk[];  // the direct walks' stacks: 4 x 128 x stk_lim words (two per lane and frame)
@@ -2133,25 +1030,11 @@ struct RowHasColumn {
         return hit;
     }
 };
-struct HasColumnCount {
-    RowHasColumn f;
-    __device__ uint64_t operator()(const uint64_t &row) const { return f(row) ? 1u : 0u; }
-};
 
-// the table the one-lane walks read: RWT, or TT for terminal records
-const uint32_t *walk_table(const RowsImage &im) { return im.term ? im.d_table3 : im.d_table; }
 
+// the context's records (record classes: the dictionary's)
 RowsView view_of(const Ctx &c) {
-    RowsView v;
-    v.blocks = (uint64_t)(uintptr_t)c.rows.blocks;
-    v.spill = (uint64_t)(uintptr_t)c.rows.spill;
-    v.magic = c.rows.magic;
-    v.num_rows = c.rows.classes ? c.rows.num_classes : c.tree.num_rows;  // (classes: the dictionary's records)
-    v.B = c.rows.B;
-    v.S = c.rows.S;
-    v.nib = c.rows.nib ? 1u : 0u;
-    v.term = c.rows.term ? 1u : 0u;
-    return v;
+    return rows_view(c.rows, c.rows.classes ? c.rows.num_classes : c.tree.num_rows);
 }
 
 using RowsFn = void (*)(RowsParams);
@@ -2400,10 +1283,7 @@ int rows_get_batch(Ctx &c, const uint64_t *d_rows, const uint64_t *d_cols, uint6
     hipLaunchKernelGGL(k_rows_get, dim3(grid256(n)), dim3(256), 0, s, view_of(c),
                        (const uint32_t *)walk_table(c.rows), d_rows, d_cols, n, c.tree.num_columns, d_out,
                        reinterpret_cast<unsigned long long *>(c.d_scalars));
-    MBRWT_HIP(hipGetLastError());
-    MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    MBRWT_HIP(hipStreamSynchronize(s));
-    return (c.h_scalars[2] & 1) ? MBRWT_ERR_RANGE : MBRWT_OK;
+    return finish_record_call(c, s);
 }
 
 int rows_count_labels(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_counts, hipStream_t s) {
@@ -2416,10 +1296,7 @@ int rows_count_labels(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_co
         hipLaunchKernelGGL(k_rows_count<false>, dim3(grid256(n)), dim3(256), 0, s, view_of(c),
                            (const uint32_t *)walk_table(c.rows), d_rows, n, reinterpret_cast<unsigned long long *>(d_counts),
                            reinterpret_cast<unsigned long long *>(c.d_scalars), (const uint32_t *)c.rows.d_table4);
-    MBRWT_HIP(hipGetLastError());
-    MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    MBRWT_HIP(hipStreamSynchronize(s));
-    return (c.h_scalars[2] & 1) ? MBRWT_ERR_RANGE : MBRWT_OK;
+    return finish_record_call(c, s);
 }
 
 int rows_count_work(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *visits, uint64_t *labels, hipStream_t s) {
@@ -2432,13 +1309,7 @@ int rows_count_work(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *visits
         hipLaunchKernelGGL(k_rows_count<true>, dim3(grid256(n)), dim3(256), 0, s, view_of(c),
                            (const uint32_t *)walk_table(c.rows), d_rows, n, nullptr,
                            reinterpret_cast<unsigned long long *>(c.d_scalars), (const uint32_t *)c.rows.d_table4);
-    MBRWT_HIP(hipGetLastError());
-    MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    MBRWT_HIP(hipStreamSynchronize(s));
-    if (c.h_scalars[2] & 1) return MBRWT_ERR_RANGE;
-    if (visits) *visits = c.h_scalars[3];
-    if (labels) *labels = c.h_scalars[4];
-    return MBRWT_OK;
+    return finish_record_call(c, s, visits, labels);
 }
 
 int rows_get_column(Ctx &c, uint64_t column, uint64_t *d_rows, uint64_t rows_cap, uint64_t *rows_needed,
@@ -2451,33 +1322,7 @@ int rows_get_column(Ctx &c, uint64_t column, uint64_t *d_rows, uint64_t rows_cap
     if (c.rows.classes) return rows_class_get_column(c, column, d_rows, rows_cap, rows_needed, s);
     const uint64_t n = c.tree.num_rows;
     const RowHasColumn f{view_of(c), walk_table(c.rows), (uint32_t)column};
-    hipcub::CountingInputIterator<uint64_t> rows_it(0);
-    // the column's size first (a reduce over the rows), then the rows
-    hipcub::TransformInputIterator<uint64_t, HasColumnCount, hipcub::CountingInputIterator<uint64_t>> cnt_it(
-        rows_it, HasColumnCount{f});
-    int rc;
-    size_t red_bytes = 0, sel_bytes = 0;
-    uint64_t *d_num = reinterpret_cast<uint64_t *>(c.d_scalars);
-    MBRWT_HIP(hipcub::DeviceReduce::Sum(nullptr, red_bytes, cnt_it, d_num, n, s));
-    if ((rc = ensure(c.ws_scan, std::max<size_t>(red_bytes, 256)))) return rc;
-    MBRWT_HIP(hipcub::DeviceReduce::Sum(c.ws_scan.buf, red_bytes, cnt_it, d_num, n, s));
-    MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    MBRWT_HIP(hipStreamSynchronize(s));
-    const uint64_t need = c.h_scalars[0];
-    if (rows_needed) *rows_needed = need;
-    if (!d_rows || need > rows_cap) {
-        if (need > rows_cap) {
-            set_error("rows_cap too small");
-            return MBRWT_ERR_CAPACITY;
-        }
-        return MBRWT_OK;
-    }
-    if (!need) return MBRWT_OK;
-    MBRWT_HIP(hipcub::DeviceSelect::If(nullptr, sel_bytes, rows_it, d_rows, d_num, n, f, s));
-    if ((rc = ensure(c.ws_scan, sel_bytes))) return rc;
-    MBRWT_HIP(hipcub::DeviceSelect::If(c.ws_scan.buf, sel_bytes, rows_it, d_rows, d_num, n, f, s));
-    MBRWT_HIP(hipStreamSynchronize(s));
-    return MBRWT_OK;
+    return select_rows(c, n, f, d_rows, rows_cap, rows_needed, s);
 }
 
 }  // namespace mbrwt

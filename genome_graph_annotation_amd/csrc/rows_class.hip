@@ -37,6 +37,7 @@
 
 #include "mbrwt_internal.hpp"
 #include "rows_record.hpp"
+#include "rows_select.hpp"
 
 namespace mbrwt {
 namespace {
@@ -214,27 +215,6 @@ struct ClassHas {
     const uint8_t *has;
     __device__ bool operator()(const uint64_t &row) const { return has[class_field(index, w, row)] != 0; }
 };
-struct ClassHasCount {
-    ClassHas f;
-    __device__ uint64_t operator()(const uint64_t &row) const { return f(row) ? 1u : 0u; }
-};
-
-uint64_t grid_of(uint64_t items) { return std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, 65536)); }
-
-// the table the record walks read: RWT, or TT for terminal records (r06)
-const uint32_t *class_table(const RowsImage &im) { return im.term ? im.d_table3 : im.d_table; }
-RowsView block_view(const RowsImage &im, uint64_t records) {
-    RowsView v;
-    v.blocks = (uint64_t)(uintptr_t)im.blocks;
-    v.spill = (uint64_t)(uintptr_t)im.spill;
-    v.magic = im.magic;
-    v.num_rows = records;
-    v.B = im.B;
-    v.S = im.S;
-    v.nib = im.nib ? 1u : 0u;
-    v.term = im.term ? 1u : 0u;
-    return v;
-}
 
 // device scratch of one build step, freed on every path out
 struct Scratch {
@@ -264,7 +244,7 @@ int rows_classes_build(RowsImage &im, uint64_t n, int mode, uint64_t *sample_dis
     // (nibble-coded records: no classes -- a compact image of rows that do not
     // repeat; the two compressions answer different data)
     if (mode == 0 || im.var || im.nib || !im.blocks || !im.d_table || n < 2 || n > (1ull << 32)) return MBRWT_OK;
-    const RowsView v = block_view(im, n);
+    const RowsView v = rows_view(im, n);
     Scratch sc;
     unsigned long long *d_err = sc.get<unsigned long long>(4);
     if (!d_err) return MBRWT_OK;  // (no room: keep the block image)
@@ -277,7 +257,7 @@ int rows_classes_build(RowsImage &im, uint64_t n, int mode, uint64_t *sample_dis
         const uint64_t m = kSampleRows, stride = n / m;
         uint64_t *k0 = sc.get<uint64_t>(m), *k1 = sc.get<uint64_t>(m), *d_cnt = sc.get<uint64_t>(1);
         if (!k0 || !k1 || !d_cnt) return MBRWT_OK;
-        hipLaunchKernelGGL(k_class_hash, dim3((unsigned)grid_of(m)), dim3(256), 0, s, v, class_table(im), 0ull, stride, m,
+        hipLaunchKernelGGL(k_class_hash, dim3(grid256(m)), dim3(256), 0, s, v, walk_table(im), 0ull, stride, m,
                            k0, (uint64_t *)nullptr, d_err);
         MBRWT_HIP(hipGetLastError());
         size_t tb = 0, rb = 0;
@@ -318,7 +298,7 @@ int rows_classes_build(RowsImage &im, uint64_t n, int mode, uint64_t *sample_dis
     uint64_t *keys_in = sc.get<uint64_t>(n), *vals_in = sc.get<uint64_t>(n);
     uint64_t *keys = sc.get<uint64_t>(n), *rows = sc.get<uint64_t>(n);
     if (!keys_in || !vals_in || !keys || !rows) return MBRWT_OK;
-    hipLaunchKernelGGL(k_class_hash, dim3((unsigned)grid_of(n)), dim3(256), 0, s, v, class_table(im), 0ull, 1ull, n,
+    hipLaunchKernelGGL(k_class_hash, dim3(grid256(n)), dim3(256), 0, s, v, walk_table(im), 0ull, 1ull, n,
                        keys_in, vals_in, d_err);
     MBRWT_HIP(hipGetLastError());
     hipcub::CountingInputIterator<uint64_t> it(0);
@@ -333,7 +313,7 @@ int rows_classes_build(RowsImage &im, uint64_t n, int mode, uint64_t *sample_dis
     MBRWT_HIP(hipMemcpyAsync(&D, cid1 + n - 1, 8, hipMemcpyDeviceToHost, s));
     MBRWT_HIP(hipStreamSynchronize(s));
     if (!D) return MBRWT_OK;
-    hipLaunchKernelGGL(k_class_reps, dim3((unsigned)grid_of(n)), dim3(256), 0, s, keys, rows, cid1, n, rep);
+    hipLaunchKernelGGL(k_class_reps, dim3(grid256(n)), dim3(256), 0, s, keys, rows, cid1, n, rep);
     MBRWT_HIP(hipGetLastError());
     uint32_t w = 1;
     while (w < 32 && (1ull << w) < D) ++w;
@@ -344,11 +324,11 @@ int rows_classes_build(RowsImage &im, uint64_t n, int mode, uint64_t *sample_dis
         return MBRWT_OK;
     }
     MBRWT_HIP(hipMemsetAsync(index, 0, index_words * 4, s));
-    hipLaunchKernelGGL(k_class_assign, dim3((unsigned)grid_of(n)), dim3(256), 0, s, v, class_table(im), rows, cid1, rep, n,
+    hipLaunchKernelGGL(k_class_assign, dim3(grid256(n)), dim3(256), 0, s, v, walk_table(im), rows, cid1, rep, n,
                        w, index, d_err);
     MBRWT_HIP(hipGetLastError());
     unsigned long long *d_acc = d_err + 1;  // [1] units, [2] spilled, [3] long
-    hipLaunchKernelGGL(k_class_measure, dim3((unsigned)grid_of(D)), dim3(256), 0, s, v, class_table(im), rep, D, d_acc);
+    hipLaunchKernelGGL(k_class_measure, dim3(grid256(D)), dim3(256), 0, s, v, walk_table(im), rep, D, d_acc);
     MBRWT_HIP(hipGetLastError());
     MBRWT_HIP(hipMemcpyAsync(h_err, d_err, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     MBRWT_HIP(hipStreamSynchronize(s));
@@ -372,7 +352,7 @@ int rows_classes_build(RowsImage &im, uint64_t n, int mode, uint64_t *sample_dis
     MBRWT_HIP(hipMemsetAsync(dblocks, 0, D * kClassB, s));
     MBRWT_HIP(hipMemsetAsync(dspill, 0, spill_cap, s));
     MBRWT_HIP(hipMemsetAsync(d_acc, 0, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(k_class_write, dim3((unsigned)grid_of(D)), dim3(256), 0, s, v, class_table(im), rep, D, dblocks,
+    hipLaunchKernelGGL(k_class_write, dim3(grid256(D)), dim3(256), 0, s, v, walk_table(im), rep, D, dblocks,
                        dspill, d_acc);
     MBRWT_HIP(hipGetLastError());
     MBRWT_HIP(hipStreamSynchronize(s));
@@ -402,7 +382,7 @@ int rows_class_map(Ctx &c, const uint64_t *d_rows, uint64_t n, const uint64_t **
     if (int rc = ensure(c.ws_class, std::max<uint64_t>(1, n) * sizeof(uint64_t))) return rc;
     uint64_t *out = static_cast<uint64_t *>(c.ws_class.buf);
     if (n) {
-        hipLaunchKernelGGL(k_class_map, dim3((unsigned)grid_of(n)), dim3(256), 0, s, d_rows, n, c.tree.num_rows,
+        hipLaunchKernelGGL(k_class_map, dim3(grid256(n)), dim3(256), 0, s, d_rows, n, c.tree.num_rows,
                            im.classes, im.class_bits, im.num_classes, out);
         MBRWT_HIP(hipGetLastError());
     }
@@ -417,35 +397,11 @@ int rows_class_get_column(Ctx &c, uint64_t column, uint64_t *d_rows, uint64_t ro
     int rc;
     if ((rc = ensure(c.ws_class, D))) return rc;
     uint8_t *has = static_cast<uint8_t *>(c.ws_class.buf);
-    hipLaunchKernelGGL(k_class_has, dim3((unsigned)grid_of(D)), dim3(256), 0, s, block_view(im, D), class_table(im), D,
+    hipLaunchKernelGGL(k_class_has, dim3(grid256(D)), dim3(256), 0, s, rows_view(im, D), walk_table(im), D,
                        (uint32_t)column, has);
     MBRWT_HIP(hipGetLastError());
     const ClassHas f{im.classes, im.class_bits, has};
-    hipcub::CountingInputIterator<uint64_t> rows_it(0);
-    hipcub::TransformInputIterator<uint64_t, ClassHasCount, hipcub::CountingInputIterator<uint64_t>> cnt_it(
-        rows_it, ClassHasCount{f});
-    size_t red_bytes = 0, sel_bytes = 0;
-    uint64_t *d_num = reinterpret_cast<uint64_t *>(c.d_scalars);
-    MBRWT_HIP(hipcub::DeviceReduce::Sum(nullptr, red_bytes, cnt_it, d_num, n, s));
-    if ((rc = ensure(c.ws_scan, std::max<size_t>(red_bytes, 256)))) return rc;
-    MBRWT_HIP(hipcub::DeviceReduce::Sum(c.ws_scan.buf, red_bytes, cnt_it, d_num, n, s));
-    MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    MBRWT_HIP(hipStreamSynchronize(s));
-    const uint64_t need = c.h_scalars[0];
-    if (rows_needed) *rows_needed = need;
-    if (!d_rows || need > rows_cap) {
-        if (need > rows_cap) {
-            set_error("rows_cap too small");
-            return MBRWT_ERR_CAPACITY;
-        }
-        return MBRWT_OK;
-    }
-    if (!need) return MBRWT_OK;
-    MBRWT_HIP(hipcub::DeviceSelect::If(nullptr, sel_bytes, rows_it, d_rows, d_num, n, f, s));
-    if ((rc = ensure(c.ws_scan, sel_bytes))) return rc;
-    MBRWT_HIP(hipcub::DeviceSelect::If(c.ws_scan.buf, sel_bytes, rows_it, d_rows, d_num, n, f, s));
-    MBRWT_HIP(hipStreamSynchronize(s));
-    return MBRWT_OK;
+    return select_rows(c, n, f, d_rows, rows_cap, rows_needed, s);
 }
 
 }  // namespace mbrwt

@@ -1,5 +1,5 @@
 // rows_emit.hpp -- the masks of a row's descent over a node image (any of
-// its kinds), in DFS pre-order: what the row-record builders (rows.hip,
+// its kinds), in DFS pre-order: what the row-record builders (rows_build.hip,
 // rows_var.hip) store per row.  Device code shared by both translation units.
 #pragma once
 

@@ -1,4 +1,4 @@
-// rows_plan.hpp -- the decisions of the row-record build (rows.hip
+// rows_plan.hpp -- the decisions of the row-record build (rows_build.hip
 // rows_build_range: choose_code, choose_layout) as pure host code: the
 // candidate block shapes, their cost model, the choice among them, the
 // record-code rule and the variable-length byte estimates.  Standard headers

@@ -19,6 +19,21 @@ struct RowsView {
     uint32_t nib;   // masks stored as nibble codes (RowsImage::nib)
     uint32_t term;  // terminal records (RowsImage::term): `table` is the TT table
 };
+// the view of a block image that holds `records` records
+inline RowsView rows_view(const RowsImage &im, uint64_t records) {
+    RowsView v;
+    v.blocks = (uint64_t)(uintptr_t)im.blocks;
+    v.spill = (uint64_t)(uintptr_t)im.spill;
+    v.magic = im.magic;
+    v.num_rows = records;
+    v.B = im.B;
+    v.S = im.S;
+    v.nib = im.nib ? 1u : 0u;
+    v.term = im.term ? 1u : 0u;
+    return v;
+}
+// the table the one-lane walks read: RWT, or TT for terminal records
+inline const uint32_t *walk_table(const RowsImage &im) { return im.term ? im.d_table3 : im.d_table; }
 __device__ __forceinline__ uint64_t rows_block(uint64_t r, uint32_t S, uint64_t magic) {
     return S == 1 ? r : __umul64hi(r, magic);
 }
@@ -137,7 +152,7 @@ __device__ bool rwt_walk(const uint32_t *table, MaskFn mask, LeafFn leaf, InnerF
     return ok;
 }
 
-// TERMINAL records (r06, MBRWT_BUILD_ROWS_CODE = 2; rows.hip
+// TERMINAL records (r06, MBRWT_BUILD_ROWS_CODE = 2; rows_tables.cpp
 // build_term_tables): a row's descent as the leaf parents and leaves it
 // reaches ("terminals"), in pre-order, each a w-bit field {terminal id
 // [0, ib), its children mask [ib, w)} packed LSB-first -- the internal

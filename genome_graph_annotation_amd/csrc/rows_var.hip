@@ -44,6 +44,8 @@
 #include "device_access.hpp"
 #include "mbrwt_internal.hpp"
 #include "rows_emit.hpp"
+#include "rows_select.hpp"
+#include "wave_scan.hpp"
 
 namespace mbrwt {
 
@@ -198,10 +200,6 @@ __global__ __launch_bounds__(256) void k_var_lines(const uint64_t *__restrict__ 
     }
 }
 
-struct U16ToU64 {
-    __host__ __device__ __forceinline__ uint64_t operator()(const uint16_t &x) const { return x; }
-};
-
 }  // namespace
 
 int var_build_range(RowsImage &im, const Ctx &range, uint64_t row0, VarScratch &ws, hipStream_t s) {
@@ -227,7 +225,7 @@ int var_build_range(RowsImage &im, const Ctx &range, uint64_t row0, VarScratch &
     hipLaunchKernelGGL(k_var_measure, dim3(grid256(nr)), dim3(256), 0, s, range.d_nodes, range.tree.folded ? 1u : 0u,
                        nr, im.d_unit_of, im.var_W, d_units, d_cnt, d_acc);
     MBRWT_HIP(hipGetLastError());
-    hipcub::TransformInputIterator<uint64_t, U16ToU64, const uint16_t *> it(d_units, U16ToU64());
+    hipcub::TransformInputIterator<uint64_t, Widen<uint16_t>, const uint16_t *> it(d_units, Widen<uint16_t>());
     size_t sb = 0;
     MBRWT_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, it, d_off, nr + 1, s));
     if ((rc = ensure(ws.scan, sb))) return rc;
@@ -411,17 +409,6 @@ __global__ __launch_bounds__(256) void k_var_locate(VarParams p) {
     }
 }
 
-__device__ __forceinline__ void var_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ void var_publish(unsigned long long *status, uint64_t st) {
-    atomicMax(&status[1], (unsigned long long)st);
-    atomicOr(&status[2], 1ull << st);
-}
-
 // k_var_decode: R = 64 / G rows per tile (one wave), G lanes per row; the
 // grid is persistent, WPB waves per workgroup share the unit table in LDS.
 // (G >= 8: tiles of <= 8 rows need < 6 KB of LDS per wave, so 24 waves per
@@ -439,7 +426,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(G >= 8
         const uint64_t err = p.scalars[2];
         p.scalars[2] = 0;
         p.status[0] = total_all;
-        var_publish(p.status, (err & 1) ? MBRWT_ERR_RANGE : total_all > p.cap ? MBRWT_ERR_CAPACITY : MBRWT_OK);
+        publish_status(p.status, (err & 1) ? MBRWT_ERR_RANGE : total_all > p.cap ? MBRWT_ERR_CAPACITY : MBRWT_OK);
     }
     if (total_all > p.cap) return;
     AS_LDS uint16_t *ubase = (AS_LDS uint16_t *)lds_var;
@@ -485,7 +472,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(G >= 8
         const bool fits = TC * 16 <= p.CR && ttot <= p.CS;
         if (fits) {
             for (uint32_t k = 0; k < nch; ++k) owner[cs + k] = (uint8_t)rr;
-            var_wave_sync();
+            wave_sync();
             // coalesced gather: lane g of round k loads chunk 64 k + g
             for (uint32_t g0 = 0; g0 < TC; g0 += 256) {
                 u32x4_t v[4];
@@ -504,7 +491,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(G >= 8
                     if (g < TC) ((AS_LDS u32x4_t *)rec)[g] = v[j];
                 }
             }
-            var_wave_sync();
+            wave_sync();
         }
         // this lane's share of the row: an equal share of its units (mask
         // bytes), found from the units in words [w0, w1) of every lane
@@ -582,7 +569,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(G >= 8
                 var_lane_labels(word_l, byte_l, wi, wv0, 4 * W + j0, labs,
                                 [&](uint32_t u) -> uint32_t { return ubase[u]; },
                                 [&](uint32_t k, uint32_t lab) { stage[pos + k] = (uint16_t)lab; });
-            var_wave_sync();
+            wave_sync();
             // the tile's labels: contiguous in the CSR, 4 per lane and store
             uint32_t *dst = p.cols + tbase;
             for (uint32_t i = 4 * lane; i < ttot; i += 256) {
@@ -597,7 +584,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(G >= 8
                     for (uint32_t j = i; j < ttot; ++j) gst(dst + j, (uint32_t)stage[j]);
                 }
             }
-            var_wave_sync();  // the stage, the chunks and the owners are reused
+            wave_sync();  // the stage, the chunks and the owners are reused
         } else {
             // a tile beyond the LDS budget: records read and labels stored
             // straight from / to global memory
@@ -700,10 +687,6 @@ struct VarHasColumn {
         return hit;
     }
 };
-struct VarHasColumnCount {
-    VarHasColumn f;
-    __device__ uint64_t operator()(const uint64_t &row) const { return f(row) ? 1u : 0u; }
-};
 
 VarView var_view(const Ctx &c) {
     VarView v;
@@ -713,10 +696,6 @@ VarView var_view(const Ctx &c) {
     v.W = c.rows.var_W;
     return v;
 }
-
-struct U32ToU64v {
-    __host__ __device__ __forceinline__ uint64_t operator()(const uint32_t &x) const { return x; }
-};
 
 using VarFn = void (*)(VarParams);
 constexpr uint32_t kVarWpb = 4;
@@ -801,7 +780,7 @@ int var_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets
     }
     uint64_t *d_loc = reinterpret_cast<uint64_t *>(c.ws_temp.buf);
     uint32_t *d_cnt = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(c.ws_temp.buf) + cnt_at);
-    hipcub::TransformInputIterator<uint64_t, U32ToU64v, const uint32_t *> it(d_cnt, U32ToU64v());
+    hipcub::TransformInputIterator<uint64_t, Widen<uint32_t>, const uint32_t *> it(d_cnt, Widen<uint32_t>());
     size_t sb = 0;
     MBRWT_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, it, d_offsets, n + 1, s));
     if ((rc = ensure(c.ws_scan, sb))) return rc;
@@ -858,10 +837,7 @@ int var_get_batch(Ctx &c, const uint64_t *d_rows, const uint64_t *d_cols, uint64
     hipLaunchKernelGGL(k_var_get, dim3(grid256(n)), dim3(256), 0, s, var_view(c),
                        (const uint32_t *)c.rows.d_var_units, d_rows, d_cols, n, c.tree.num_columns, d_out,
                        reinterpret_cast<unsigned long long *>(c.d_scalars));
-    MBRWT_HIP(hipGetLastError());
-    MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    MBRWT_HIP(hipStreamSynchronize(s));
-    return (c.h_scalars[2] & 1) ? MBRWT_ERR_RANGE : MBRWT_OK;
+    return finish_record_call(c, s);
 }
 
 int var_count(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_counts, uint64_t *visits, uint64_t *labels,
@@ -877,13 +853,7 @@ int var_count(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_counts, ui
                            (const DevNode *)c.d_nodes, d_rows, n, reinterpret_cast<unsigned long long *>(d_counts),
                            reinterpret_cast<unsigned long long *>(c.d_scalars));
     }
-    MBRWT_HIP(hipGetLastError());
-    MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    MBRWT_HIP(hipStreamSynchronize(s));
-    if (c.h_scalars[2] & 1) return MBRWT_ERR_RANGE;
-    if (visits) *visits = c.h_scalars[3];
-    if (labels) *labels = c.h_scalars[4];
-    return MBRWT_OK;
+    return finish_record_call(c, s, visits, labels);
 }
 
 int var_get_column(Ctx &c, uint64_t column, uint64_t *d_rows, uint64_t rows_cap, uint64_t *rows_needed,
@@ -894,32 +864,7 @@ int var_get_column(Ctx &c, uint64_t column, uint64_t *d_rows, uint64_t rows_cap,
     }
     const uint64_t n = c.tree.num_rows;
     const VarHasColumn f{var_view(c), c.rows.d_var_units, (uint32_t)column};
-    hipcub::CountingInputIterator<uint64_t> rows_it(0);
-    hipcub::TransformInputIterator<uint64_t, VarHasColumnCount, hipcub::CountingInputIterator<uint64_t>> cnt_it(
-        rows_it, VarHasColumnCount{f});
-    int rc;
-    size_t red_bytes = 0, sel_bytes = 0;
-    uint64_t *d_num = reinterpret_cast<uint64_t *>(c.d_scalars);
-    MBRWT_HIP(hipcub::DeviceReduce::Sum(nullptr, red_bytes, cnt_it, d_num, n, s));
-    if ((rc = ensure(c.ws_scan, std::max<size_t>(red_bytes, 256)))) return rc;
-    MBRWT_HIP(hipcub::DeviceReduce::Sum(c.ws_scan.buf, red_bytes, cnt_it, d_num, n, s));
-    MBRWT_HIP(hipMemcpyAsync(c.h_scalars, c.d_scalars, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    MBRWT_HIP(hipStreamSynchronize(s));
-    const uint64_t need = c.h_scalars[0];
-    if (rows_needed) *rows_needed = need;
-    if (!d_rows || need > rows_cap) {
-        if (need > rows_cap) {
-            set_error("rows_cap too small");
-            return MBRWT_ERR_CAPACITY;
-        }
-        return MBRWT_OK;
-    }
-    if (!need) return MBRWT_OK;
-    MBRWT_HIP(hipcub::DeviceSelect::If(nullptr, sel_bytes, rows_it, d_rows, d_num, n, f, s));
-    if ((rc = ensure(c.ws_scan, sel_bytes))) return rc;
-    MBRWT_HIP(hipcub::DeviceSelect::If(c.ws_scan.buf, sel_bytes, rows_it, d_rows, d_num, n, f, s));
-    MBRWT_HIP(hipStreamSynchronize(s));
-    return MBRWT_OK;
+    return select_rows(c, n, f, d_rows, rows_cap, rows_needed, s);
 }
 
 }  // namespace mbrwt

@@ -1,4 +1,5 @@
-// wave_scan.hpp -- wave64 prefix sums in VALU (DPP), for gfx950.
+// wave_scan.hpp -- wave64 helpers for gfx950: prefix sums in VALU (DPP), the wave
+// barrier, the status publication, the widening functor of the device scans.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -28,5 +29,25 @@ __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t x) {
 #else
 __device__ uint32_t wave_incl_sum(uint32_t x);  // (the host pass only parses the kernels)
 #endif
+
+// the lanes of one wave exchange data through LDS (or global memory): what
+// every lane wrote before is visible to every lane after
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// a call's status block {total, status, sticky bits}: the status only rises
+__device__ __forceinline__ void publish_status(unsigned long long *status, uint64_t st) {
+    atomicMax(&status[1], (unsigned long long)st);
+    atomicOr(&status[2], 1ull << st);
+}
+
+// narrow counts read as u64 (the input of a device scan with u64 sums)
+template <class T>
+struct Widen {
+    __host__ __device__ __forceinline__ uint64_t operator()(const T &x) const { return x; }
+};
 
 }  // namespace mbrwt

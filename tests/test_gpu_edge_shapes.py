@@ -14,9 +14,14 @@ get_rows (csrc/rows.hip k_traverse_rows -> k_compact_tiles):
   * four tiles per compaction wave, a partial last tile, offsets[n] stored by
     lane nr - 1: geometry
   * the labels-per-row limit of the 15-bit temp count: test_labels_per_row_limit
+get_column's capacity protocol (csrc/rows_select.hpp) and the point queries'
+empty batch / one row / row == num_rows (finish_record_call), on a block, a
+variable-length and a record-class form: test_get_column_capacity_protocol,
+test_point_queries_protocol.
 classify (csrc/classify.hip): test_classify_*.
 The untested fallback of a ranged build: test_ranged_terminal_limit.
 """
+import contextlib
 import math
 
 import numpy as np
@@ -261,6 +266,158 @@ def test_staircase_rows(oracle_mod, build_env, name):
     _all_batches(dev, case, m)
     if expect == "classes":  # the repeated rows
         _check_batch(dev, case, np.arange(case.n, dtype=np.uint64)[::-1], "every row, reversed")
+
+
+# ---- the small drivers the three record forms share ----------------------------
+
+_FORMS = {"blocks": "byte-masks", "variable": "var-8", "classes": "classes"}   # form -> its _CONFIGS entry
+_forms = {}
+
+
+def _short_staircase(O, name):
+    """The staircase of _CONFIGS[name] with its last column cleared: the
+    longest row is shorter than the width, so no row holds column m - 1."""
+    m, pad, kind, (part, arity, relax), _, _, _ = _CONFIGS[name]
+    key = ("short", m, pad, kind, part, arity, relax)
+    if key not in _cases:
+        dense = E.staircase(m, pad, kind is True)
+        dense[:, m - 1] = False
+        _cases[key] = _Case(O, dense, part, arity, relax)
+    return _cases[key]
+
+
+def _record_form(O, build_env, form):
+    """One built form of the short staircase under the build options of its
+    _CONFIGS entry, asserted through rows_stats(); shared by the tests below."""
+    from genome_graph_annotation_amd import BRWTDevice, _lib as L
+    from genome_graph_annotation_amd.brwt import build_option
+    case = _short_staircase(O, _FORMS[form])
+    if form not in _forms:
+        opts = dict(_CONFIGS[_FORMS[form]][5])
+        classes = opts.pop("classes", None)
+        for k, v in opts.items():
+            build_env(k, v)
+        with build_option(L.MBRWT_BUILD_ROWS_CLASSES, classes) if classes is not None else contextlib.nullcontext():
+            dev = BRWTDevice.from_tree(case.ex, layout="rows")
+        st = dev.rows_stats()
+        assert dev.layout() == "rows", dev.layout()
+        assert bool(st["variable"]) == (form == "variable"), st
+        assert (st.get("classes", 0) > 0) == (form == "classes"), st
+        _forms[form] = dev
+    return _forms[form], case
+
+
+@pytest.mark.parametrize("form", list(_FORMS))
+def test_get_column_capacity_protocol(oracle_mod, build_env, form):
+    """mbrwt_get_column_device on each record form (include/mbrwt.h): a null
+    buffer sizes the column -- *rows_needed = its rows, MBRWT_OK for a column
+    no row holds, MBRWT_ERR_CAPACITY otherwise (rows_cap counts as 0); rows_cap
+    one short is MBRWT_ERR_CAPACITY with the size and 'rows_cap too small';
+    rows_cap = the size gives the oracle's ascending rows and writes nothing
+    past them; column == num_columns is MBRWT_ERR_RANGE."""
+    import ctypes as C
+    import torch
+    from genome_graph_annotation_amd import _lib as L
+    dev, case = _record_form(oracle_mod, build_env, form)
+    lib, m = L.lib(), case.m
+
+    def call(col, buf, cap):
+        need = C.c_uint64(2**64 - 1)
+        st = lib.mbrwt_get_column_device(dev._h, col, buf.data_ptr() if buf is not None else None, cap,
+                                         C.byref(need), None)
+        torch.cuda.synchronize()
+        return st, int(need.value), (lib.mbrwt_last_error_message() or b"").decode()
+
+    copies = case.n // (m + 1)
+    for col in (0, 254, m - 2):
+        want = np.asarray(case.t.get_column(col), dtype=np.uint64)
+        np.testing.assert_array_equal(want, np.nonzero(case.dense[:, col])[0])
+        k = len(want)
+        assert k == (m - col) * copies > 0   # rows col + 1 .. m of every copy of the staircase
+        st, need, msg = call(col, None, 0)
+        print(form, col, "null buffer:", st, need)
+        assert (st, need) == (L.MBRWT_ERR_CAPACITY, k) and "rows_cap too small" in msg, (col, st, need, msg)
+        buf = torch.full((k + 8,), -1, dtype=torch.int64, device="cuda")
+        st, need, msg = call(col, buf, k - 1)
+        assert (st, need) == (L.MBRWT_ERR_CAPACITY, k) and "rows_cap too small" in msg, (col, st, need, msg)
+        assert "rows_cap too small" in L.MBRWTError(st).args[0]
+        assert (buf == -1).all(), "rows written under MBRWT_ERR_CAPACITY"
+        st, need, _ = call(col, buf, k)
+        assert (st, need) == (L.MBRWT_OK, k), (col, st, need)
+        np.testing.assert_array_equal(buf[:k].cpu().numpy().view(np.uint64), want, err_msg=f"column {col}")
+        assert (buf[k:] == -1).all(), "a row written past the column's size"
+        np.testing.assert_array_equal(dev.get_column(col), want, err_msg=f"column {col} (host)")
+    # the column no row holds
+    assert not case.dense[:, m - 1].any() and len(case.t.get_column(m - 1)) == 0
+    assert call(m - 1, None, 0)[:2] == (L.MBRWT_OK, 0)
+    buf = torch.full((8,), -1, dtype=torch.int64, device="cuda")
+    assert call(m - 1, buf, 8)[:2] == (L.MBRWT_OK, 0) and (buf == -1).all()
+    assert len(dev.get_column(m - 1)) == 0
+    # column == num_columns
+    assert dev.num_columns() == m
+    st, _, msg = call(m, buf, 8)
+    assert st == L.MBRWT_ERR_RANGE and "column out of range" in msg, (st, msg)
+    assert call(m, None, 0)[0] == L.MBRWT_ERR_RANGE
+
+
+@pytest.mark.parametrize("form", list(_FORMS))
+def test_point_queries_protocol(oracle_mod, build_env, form):
+    """get_batch, count_labels and the work count (V, L) on each record form:
+    an empty batch, one in-range row, and a batch whose last row is num_rows
+    (MBRWT_ERR_RANGE)."""
+    import ctypes as C
+    import torch
+    from genome_graph_annotation_amd import _lib as L
+    dev, case = _record_form(oracle_mod, build_env, form)
+    lib, m, n = L.lib(), case.m, case.n
+    assert dev.num_rows() == n
+
+    def dev_rows(rows):
+        return torch.from_numpy(np.asarray(rows, dtype=np.uint64).view(np.int64)).cuda()
+
+    def get_batch(rows, cols):
+        rt, ct = dev_rows(rows), dev_rows(cols)
+        out = torch.full((max(1, len(rows)),), 7, dtype=torch.uint8, device="cuda")
+        st = lib.mbrwt_get_batch_device(dev._h, rt.data_ptr(), ct.data_ptr(), len(rows), out.data_ptr(), None)
+        torch.cuda.synchronize()
+        return st, out.cpu().numpy()
+
+    def count_labels(rows):
+        rt = dev_rows(rows)
+        cnt = torch.full((m,), 7, dtype=torch.int64, device="cuda")
+        st = lib.mbrwt_count_labels_device(dev._h, rt.data_ptr(), len(rows), cnt.data_ptr(), None)
+        torch.cuda.synchronize()
+        return st, cnt.cpu().numpy()
+
+    def count_work(rows):
+        rt = dev_rows(rows)
+        v, lab = C.c_uint64(2**64 - 1), C.c_uint64(2**64 - 1)
+        st = lib.mbrwt_count_work_device(dev._h, rt.data_ptr(), len(rows), C.byref(v), C.byref(lab), None)
+        return st, int(v.value), int(lab.value)
+
+    # n = 0
+    st, out = get_batch([], [])
+    assert st == L.MBRWT_OK and (out == 7).all()
+    st, cnt = count_labels([])
+    assert st == L.MBRWT_OK and (cnt == 0).all()
+    assert count_work([]) == (L.MBRWT_OK, 0, 0)
+    # one in-range row: row r holds the columns [0, r)
+    r = 300
+    assert case.counts[r] == r
+    st, out = get_batch([r, r], [r - 1, r])
+    assert st == L.MBRWT_OK and out.tolist() == [1, 0]
+    st, cnt = count_labels([r])
+    assert st == L.MBRWT_OK
+    np.testing.assert_array_equal(cnt, (np.arange(m) < r).astype(np.int64))
+    _, cols_o, vis = case.t.get_rows(np.array([r], dtype=np.uint64), with_visits=True)
+    assert len(cols_o) == r
+    assert count_work([r]) == (L.MBRWT_OK, int(vis.sum()), r)
+    # the last row of the batch is num_rows
+    assert get_batch([r, 0, n], [0, 0, 0])[0] == L.MBRWT_ERR_RANGE
+    assert count_labels([r, 0, n])[0] == L.MBRWT_ERR_RANGE
+    assert count_work([r, 0, n])[0] == L.MBRWT_ERR_RANGE
+    # (and the context still answers)
+    assert get_batch([r], [0])[1].tolist() == [1]
 
 
 # ---- the labels-per-row limit of the records ------------------------------------

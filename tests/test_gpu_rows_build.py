@@ -1,4 +1,4 @@
-"""The decisions of whole row-record builds (csrc/rows.hip rows_build_*:
+"""The decisions of whole row-record builds (csrc/rows_build.hip rows_build_*:
 record code, block shape, tolerance, block override, variable-length records,
 the AUTO decline, ranged builds) pinned to recorded values: every case builds
 one small image and compares layout() and rows_stats() with
