@@ -298,6 +298,10 @@ __global__ void k_wt_get(WtParams P, const uint64_t *__restrict__ rows, const ui
             out[i] = 0;
             continue;
         }
+        if (col > 0xFFFFFFFFull) {  // ids are 32 bits: no row holds such a column (its low bits name another)
+            out[i] = 0;
+            continue;
+        }
         const WtChunkDev *ch = P.chunks + (row >> P.log2_rows);
         uint32_t s = (uint32_t)(P.offsets[row] - ch->str0), e = (uint32_t)(P.offsets[row + 1] - ch->str0);
         for (uint32_t l = 0; l < P.levels && s < e; ++l) {
@@ -694,7 +698,7 @@ int wt_get_column(WtCtx &c, uint64_t column, uint64_t *d_rows, uint64_t cap, uin
         return MBRWT_ERR_RANGE;
     }
     const uint64_t nch = c.chunks.size();
-    if (!nch) {
+    if (!nch || column > 0xFFFFFFFFull) {  // ids are 32 bits: a column >= 2^32 is in range and empty
         if (needed) *needed = 0;
         return MBRWT_OK;
     }

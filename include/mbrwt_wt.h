@@ -31,7 +31,15 @@ extern "C" {
 typedef struct mbrwt_wt mbrwt_wt;
 
 /* CSR rows: row r's column ids are cols[offsets[r] .. offsets[r+1]) in any
- * order; offsets has num_rows + 1 entries, offsets[0] = 0. */
+ * order; offsets has num_rows + 1 entries, offsets[0] = 0.
+ *
+ * num_columns is open, as the reference's (a uint64_t): it may exceed 2^32.
+ * The ids are 32 bits wide, so no row can hold a column >= 2^32; such a
+ * column below num_columns is in range and empty -- mbrwt_wt_get_batch
+ * answers 0 for it and mbrwt_wt_get_column no rows (MBRWT_OK, *rows_needed =
+ * 0); a column >= num_columns is MBRWT_ERR_RANGE as ever.  (Only
+ * mbrwt_wt_create_synthetic, whose generator walks every column, refuses
+ * num_columns > 2^32 - 1.) */
 typedef struct mbrwt_binrel_desc {
     uint64_t num_rows;
     uint64_t num_columns;

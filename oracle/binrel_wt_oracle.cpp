@@ -73,7 +73,11 @@ struct Bits {
     }
 };
 
-// levelwise wavelet tree over symbols < 2^L (sdsl::wt_int semantics)
+// x >> s for any s (a shift by the type's width or more is undefined in C++;
+// L reaches 33 at num_columns = 2^32, one more than the 32-bit symbols)
+inline uint32_t shr(uint32_t x, uint32_t s) { return s >= 32 ? 0u : x >> s; }
+
+// levelwise wavelet tree over symbols < 2^L, L <= 33 (sdsl::wt_int semantics)
 struct WaveletTree {
     uint64_t n = 0;
     uint32_t L = 1;
@@ -88,19 +92,19 @@ struct WaveletTree {
             const uint32_t sh = L - 1 - l;
             lev[l].init(n);
             for (uint64_t i = 0; i < n; ++i)
-                if ((seq[i] >> sh) & 1) lev[l].set(i);
+                if (shr(seq[i], sh) & 1) lev[l].set(i);
             lev[l].finalize();
             // stable partition inside every node interval (= stable sort by the top l+1 bits)
             uint64_t i = 0;
             while (i < n) {
-                const uint32_t prefix = l ? (seq[i] >> (sh + 1)) : 0;
+                const uint32_t prefix = l ? shr(seq[i], sh + 1) : 0;
                 uint64_t e = i;
-                while (e < n && (l ? (seq[e] >> (sh + 1)) : 0) == prefix) ++e;
+                while (e < n && (l ? shr(seq[e], sh + 1) : 0) == prefix) ++e;
                 uint64_t o = i;
                 for (uint64_t k = i; k < e; ++k)
-                    if (!((seq[k] >> sh) & 1)) next[o++] = seq[k];
+                    if (!(shr(seq[k], sh) & 1)) next[o++] = seq[k];
                 for (uint64_t k = i; k < e; ++k)
-                    if ((seq[k] >> sh) & 1) next[o++] = seq[k];
+                    if (shr(seq[k], sh) & 1) next[o++] = seq[k];
                 i = e;
             }
             seq.swap(next);
@@ -109,12 +113,12 @@ struct WaveletTree {
 
     // occurrences of c in [0, i)
     uint64_t rank(uint64_t i, uint32_t c) const {
-        if (c >> L) return 0;
+        if (shr(c, L)) return 0;
         uint64_t s0 = 0, size = n, pos = std::min(i, n);
         for (uint32_t l = 0; l < L; ++l) {
             const Bits &B = lev[l];
             const uint64_t ob = B.rank1(s0), op = B.rank1(s0 + pos) - ob, on = B.rank1(s0 + size) - ob;
-            if ((c >> (L - 1 - l)) & 1) {
+            if (shr(c, L - 1 - l) & 1) {
                 s0 += size - on;
                 size = on;
                 pos = op;
@@ -134,7 +138,7 @@ struct WaveletTree {
             start[l] = s0;
             const Bits &B = lev[l];
             const uint64_t ob = B.rank1(s0), on = B.rank1(s0 + size) - ob;
-            if ((c >> (L - 1 - l)) & 1) {
+            if (shr(c, L - 1 - l) & 1) {
                 s0 += size - on;
                 size = on;
             } else {
@@ -144,7 +148,7 @@ struct WaveletTree {
         uint64_t pos = k - 1;  // inside the leaf interval
         for (uint32_t l = L; l-- > 0;) {
             const Bits &B = lev[l];
-            if ((c >> (L - 1 - l)) & 1) pos = B.select1(B.rank1(start[l]) + pos + 1) - start[l];
+            if (shr(c, L - 1 - l) & 1) pos = B.select1(B.rank1(start[l]) + pos + 1) - start[l];
             else pos = B.select0(B.rank0(start[l]) + pos + 1) - start[l];
         }
         return pos;

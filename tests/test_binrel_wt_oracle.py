@@ -57,6 +57,37 @@ def test_unsorted_and_repeated_ids(oracle_mod):
     assert t.get(1, 2) and not t.get(1, 0)
 
 
+@pytest.mark.parametrize("m", [(1 << 31) - 1, 1 << 31, (1 << 32) - 1, 1 << 32])
+def test_wide_symbols_against_numpy(oracle_mod, m):
+    """31-, 32- and 33-level trees (code_length(num_columns) reaches 33 at
+    2^32 columns, one more than the 32-bit symbols) on the chunk-per-row / w32
+    CSRs of tests/wt_shapes.py, against the numpy reference over the CSR: the
+    rows, every present column, present and absent get.  Before the shifts by
+    L and by L - 1 - l were guarded, rank() tested `c >> 32` on a u32, and
+    get / get_column were wrong at 2^31 and 2^32 - 1 columns."""
+    import wt_shapes as S
+    off, cols = S.chunk_per_row(m)
+    t = oracle_mod.OracleWT.from_csr(off, cols, m)
+    n = len(off) - 1
+    assert t.num_rows() == n and t.num_columns() == m and t.num_relations() == len(cols)
+    rows = np.concatenate([np.arange(n), np.arange(n)[::-1]]).astype(np.uint64)
+    r_off, r_cols = S.ref_rows(off, cols, rows)
+    o_off, o_cols = t.get_rows(rows)
+    np.testing.assert_array_equal(o_off, r_off)
+    np.testing.assert_array_equal(o_cols, r_cols)
+    for c in np.unique(cols).tolist():
+        np.testing.assert_array_equal(t.get_column(c), S.ref_column(off, cols, c), err_msg=f"column {c}")
+    for c in S.absent_columns(cols, m):
+        assert len(t.get_column(c)) == 0, c
+    qr, qc, want = S.point_queries(off, cols, m)
+    assert want.any() and not want.all()
+    got = np.array([t.get(int(r), int(c)) for r, c in zip(qr, qc)])
+    np.testing.assert_array_equal(got, want)
+    np.testing.assert_array_equal(S.ref_get(off, cols, qr, qc), want)
+    with pytest.raises(IndexError):
+        t.get_column(m)
+
+
 def _mix64(z):
     M = (1 << 64) - 1
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M

@@ -1,9 +1,10 @@
 """GPU parity of the BinRel-WT engine (include/mbrwt_wt.h) against the
 BinRel-WT(sdsl) oracle: get_row / get / get_column, bit-exact (integer work,
 no tolerance).  Cases: the reference's grids (test_bin_rel_wt_sdsl.cpp:86-176),
-random matrices over 1..3,173 columns (several chunks, 1..12-bit symbols),
+random matrices over 1..3,173 columns (1..12-bit symbols, one chunk each),
 unsorted input rows, error and capacity paths, and the device-generated
-synthetic matrix against the oracle's independent generator."""
+synthetic matrix against the oracle's independent generator.  The chunk,
+rank-block and symbol-width boundaries: test_gpu_binrel_wt_edges.py."""
 import numpy as np
 import pytest
 
@@ -57,7 +58,7 @@ def test_reference_grids(oracle_mod, kind):
     (3000, 256, 0.2),      # 8-bit boundary
     (3000, 257, 0.2),      # 9-bit symbols
     (2000, 40, 1.0),       # dense rows
-    (1_100_000, 3, 0.4),   # several row chunks (2^k rows per chunk)
+    (1_100_000, 3, 0.4),   # one chunk (2^24 rows a chunk at 3 columns); test_gpu_binrel_wt_edges.py has the chunked ones
 ])
 def test_random_matrices(oracle_mod, n, m, dens):
     from genome_graph_annotation_amd import BinRelWTDevice
@@ -133,6 +134,11 @@ def test_synthetic_matches_oracle(oracle_mod, n, m, dens):
     if n <= 300_000:  # the oracle's own wavelet tree over the same rows
         t = O.OracleWT.from_csr(off, cols, m)
         _compare(O, t, d, q[:20000], rng.integers(0, m, 8))
+    else:  # (4 chunks of 2^19 rows) get_column against numpy over the generator's CSR
+        for c in rng.integers(0, m, 8):
+            want = np.searchsorted(off, np.nonzero(cols == c)[0], "right") - 1
+            assert len(set((want >> 19).tolist())) == 4
+            np.testing.assert_array_equal(d.get_column(int(c)), want, err_msg=f"column {c}")
 
 
 @pytest.mark.parametrize("ratio,num_top", [(0.0, 2**64 - 1), (0.5, 3), (1.0, 1)])
