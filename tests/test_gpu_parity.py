@@ -538,7 +538,11 @@ def test_device_builder_pass_through_nodes(oracle_mod, m):
 
 # ---- binary_grouping_greedy on the device (partitionings.cpp:148-196) ----
 
-def _same_tree(a, b):
+def _same_tree(a, b, index_columns=False):
+    """The same shape; index_columns: the same index lengths and words too."""
+    if index_columns:
+        from build_shapes import same_tree
+        return same_tree(a, b)
     for k in ("num_children", "first_child", "leaf_column"):
         np.testing.assert_array_equal(np.asarray(a[k]), np.asarray(b[k]), err_msg=k)
 
@@ -551,7 +555,7 @@ def _same_tree(a, b):
 ])
 def test_device_greedy_builder_matches_reference(oracle_mod, n, m, d, relax):
     """mbrwt_create_from_columns[_relaxed] with MBRWT_PARTITIONER_GREEDY builds
-    the oracle's greedy (+ relax) tree: the same tree (exported shape), the same
+    the oracle's greedy (+ relax) tree: the same tree (shape and index columns), the same
     image bytes, the same answers."""
     from genome_graph_annotation_amd import BRWTDevice
     O = oracle_mod
@@ -560,7 +564,7 @@ def test_device_greedy_builder_matches_reference(oracle_mod, n, m, d, relax):
     t = O.OracleTree(O.lib().oracle_build_from_columns(O._p64(words), n, m, 1, 2, relax))
     built = BRWTDevice.from_columns(words[: m * W].reshape(m, W), n, 2, relax_max_arity=relax, partitioner="greedy")
     ref = BRWTDevice.from_tree(t.export())
-    _same_tree(built.export(), t.export())
+    _same_tree(built.export(), t.export(), index_columns=True)
     assert built.device_bytes() == ref.device_bytes()
     rows = np.random.default_rng(3).integers(0, n, 20000).astype(np.uint64)
     _check_rows(t, built, rows, variants=(0,))
