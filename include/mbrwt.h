@@ -514,7 +514,10 @@ int mbrwt_count_work_device(mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n, 
 /*
  * Bit-packing of n values < 2^bits (bits in 1..32) into ceil(n*bits/32) u32
  * words (value i at bits [i*bits, (i+1)*bits), LSB-first), and back; device
- * buffers, launched on `stream`.  The all-gatherv that reassembles a sharded
+ * buffers, launched on `stream`.  Only the low `bits` bits of a value (here,
+ * and of a label or a row count in mbrwt_pack_csr_device) reach the wire: a
+ * value with higher bits set is packed as its low bits and never disturbs a
+ * neighbouring value.  The all-gatherv that reassembles a sharded
  * batch's CSR (genome_graph_annotation_amd/dist.py) ships labels and row
  * counts at ceil(log2(num_columns)) bits with these.  No reference
  * counterpart (the reference has no multi-GPU path).
