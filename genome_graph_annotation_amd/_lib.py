@@ -197,6 +197,11 @@ SIGNATURES = {
                                         u64p, C.c_void_p]),
     "mbrwt_get_rows_device_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                               C.c_uint64, C.c_void_p, C.c_void_p]),
+    "mbrwt_get_rows16": (C.c_int, [C.c_void_p, u64p, C.c_uint64, u64p, C.POINTER(C.c_uint16), C.c_uint64, u64p]),
+    "mbrwt_get_rows16_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                          u64p, C.c_void_p]),
+    "mbrwt_get_rows16_device_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                C.c_uint64, C.c_void_p, C.c_void_p]),
     "mbrwt_get_column": (C.c_int, [C.c_void_p, C.c_uint64, u64p, C.c_uint64, u64p]),
     "mbrwt_get_column_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_void_p]),
     "mbrwt_get_batch": (C.c_int, [C.c_void_p, u64p, u64p, C.c_uint64, u8p]),

@@ -374,6 +374,25 @@ class BRWTDevice:
             L.check(st, "mbrwt_get_rows")
             return offsets, cols[: need.value]
 
+    def get_rows16(self, rows):
+        """get_rows with 16-bit labels (mbrwt_get_rows16; at most 65,536
+        columns) -> (offsets[n+1] uint64, cols uint16)."""
+        lib = L.lib()
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        n = len(rows)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        need = C.c_uint64(0)
+        cap = max(16, n * 16)
+        while True:
+            cols = np.zeros(cap, dtype=np.uint16)
+            st = lib.mbrwt_get_rows16(self._h, _p(rows, C.c_uint64), n, _p(offsets, C.c_uint64),
+                                      _p(cols, C.c_uint16), cap, C.byref(need))
+            if st == L.MBRWT_ERR_CAPACITY:
+                cap = int(need.value)
+                continue
+            L.check(st, "mbrwt_get_rows16")
+            return offsets, cols[: need.value]
+
     def get_row(self, row):
         off, cols = self.get_rows(np.array([row], dtype=np.uint64))
         return cols.tolist()
@@ -436,6 +455,37 @@ class BRWTDevice:
         L.check(L.lib().mbrwt_get_rows_device_async(self._h, rows_t.data_ptr(), rows_t.numel(), offsets_t.data_ptr(),
                                                     cols_t.data_ptr(), cols_t.numel(), status_t.data_ptr(), stream),
                 "mbrwt_get_rows_device_async")
+
+    @staticmethod
+    def _cols16(cols_t):
+        # torch's uint16 support is partial: int16 on the device, viewed as uint16 in numpy
+        if cols_t is None:  # count only
+            return None, 0
+        if str(cols_t.dtype) != "torch.int16":
+            raise TypeError(f"cols_t must be a torch.int16 tensor (u16 labels), not {cols_t.dtype}")
+        return cols_t.data_ptr(), cols_t.numel()
+
+    def get_rows16_device(self, rows_t, offsets_t, cols_t, stream=None):
+        """get_rows_device with 16-bit labels: cols_t is an int16 [cap] cuda
+        tensor (None: count only), any 2-byte alignment.  Returns the number
+        of labels; raises on capacity."""
+        ptr, cap = self._cols16(cols_t)
+        need = C.c_uint64(0)
+        st = L.lib().mbrwt_get_rows16_device(self._h, rows_t.data_ptr(), rows_t.numel(), offsets_t.data_ptr(),
+                                             ptr, cap, C.byref(need), stream if stream is not None else None)
+        if st == L.MBRWT_ERR_CAPACITY:
+            e = L.MBRWTError(st, "mbrwt_get_rows16_device")
+            e.needed = int(need.value)
+            raise e
+        L.check(st, "mbrwt_get_rows16_device")
+        return int(need.value)
+
+    def get_rows16_device_async(self, rows_t, offsets_t, cols_t, status_t, stream=None):
+        """get_rows_device_async with 16-bit labels (cols_t: int16 [cap])."""
+        ptr, cap = self._cols16(cols_t)
+        L.check(L.lib().mbrwt_get_rows16_device_async(self._h, rows_t.data_ptr(), rows_t.numel(),
+                                                      offsets_t.data_ptr(), ptr, cap, status_t.data_ptr(), stream),
+                "mbrwt_get_rows16_device_async")
 
     def get_batch_device(self, rows_t, cols_t, out_t, stream=None):
         L.check(L.lib().mbrwt_get_batch_device(self._h, rows_t.data_ptr(), cols_t.data_ptr(), rows_t.numel(),

@@ -351,6 +351,40 @@ class BRWTDevice : public BinaryMatrix {
         }
     }
 
+    // get_rows with 16-bit labels (mbrwt_get_rows16: half the bytes
+    // downloaded and held; matrices of at most 65,536 columns, else
+    // MBRWTException with MBRWT_ERR_UNSUPPORTED)
+    std::vector<std::vector<uint16_t>> get_rows16(const std::vector<Row> &rows) const {
+        std::vector<uint64_t> offsets;
+        std::vector<uint16_t> cols;
+        get_rows16_csr(rows, &offsets, &cols);
+        std::vector<std::vector<uint16_t>> out(rows.size());
+        for (size_t i = 0; i < rows.size(); ++i) out[i].assign(cols.begin() + offsets[i], cols.begin() + offsets[i + 1]);
+        return out;
+    }
+    void get_rows16_csr(const std::vector<Row> &rows, std::vector<uint64_t> *offsets,
+                        std::vector<uint16_t> *cols) const {
+        if (!ctx_) {
+            if (!rows.empty()) throw std::out_of_range("get_row on an empty BRWT");
+            offsets->assign(1, 0);
+            cols->clear();
+            return;
+        }
+        offsets->assign(rows.size() + 1, 0);
+        uint64_t cap = std::max<uint64_t>(16, 16 * rows.size()), need = 0;
+        for (;;) {
+            cols->resize(cap);
+            int st = mbrwt_get_rows16(ctx_.get(), rows.data(), rows.size(), offsets->data(), cols->data(), cap, &need);
+            if (st == MBRWT_ERR_CAPACITY) {
+                cap = need;
+                continue;
+            }
+            check_status(st, "BRWTDevice::get_rows16");
+            cols->resize(need);
+            return;
+        }
+    }
+
     // BRWT::load (BRWT.cpp:87-111): the BRWT stream at the stream's position
     // (mbrwt_load); false on a bad stream, like the reference
     bool load(std::istream &in) override {

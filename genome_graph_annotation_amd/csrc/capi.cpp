@@ -99,7 +99,7 @@ static void release(Ctx *c) {
     }
     for (Workspace *w : {&c->ws_temp, &c->ws_counts, &c->ws_ovf, &c->ws_scan, &c->ws_rows, &c->ws_out, &c->ws_sort,
                          &c->ws_cls_off, &c->ws_cls_cols, &c->ws_class, &c->ws_sh_keys, &c->ws_sh_local, &c->ws_sh_cnt,
-                         &c->ws_sh_sort, &c->ws_sh_tmp})
+                         &c->ws_sh_sort, &c->ws_sh_tmp, &c->ws_cols16})
         if (w->buf) (void)hipFree(w->buf);
     free_host_pipe(c->pipe);
     if (c->d_scalars) (void)hipFree(c->d_scalars);
@@ -785,6 +785,72 @@ int mbrwt_get_rows(mbrwt_ctx *ctx, const uint64_t *rows, uint64_t n, uint64_t *o
         return host_get_rows(c, rows, n, offsets, cols, cols ? cols_cap : 0, cols_needed);
     } catch (...) {
         set_error("unexpected exception in mbrwt_get_rows");
+        return MBRWT_ERR_INVALID;
+    }
+}
+
+// u16 labels: the three calls above with a narrow `cols` (contexts of at most 65,536 columns)
+int mbrwt_get_rows16_device(mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, uint16_t *d_cols,
+                            uint64_t cols_cap, uint64_t *cols_needed, void *stream) {
+    if (!ctx || (n && (!d_rows || !d_offsets)) || (!n && !d_offsets)) {
+        set_error("invalid argument");
+        return MBRWT_ERR_INVALID;
+    }
+    Ctx &c = *C(ctx);
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (!rows16_supported(c)) return MBRWT_ERR_UNSUPPORTED;
+    WsFence fence_(c.fence, reinterpret_cast<hipStream_t>(stream));
+    try {
+        if (hipSetDevice(c.device) != hipSuccess) return hip_fail(hipGetLastError(), "hipSetDevice");
+        return run_get_rows16(c, d_rows, n, d_offsets, d_cols, d_cols ? cols_cap : 0, cols_needed,
+                              reinterpret_cast<hipStream_t>(stream));
+    } catch (...) {
+        set_error("unexpected exception in mbrwt_get_rows16_device");
+        return MBRWT_ERR_INVALID;
+    }
+}
+
+int mbrwt_get_rows16_device_async(mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets,
+                                  uint16_t *d_cols, uint64_t cols_cap, uint64_t *d_status, void *stream) {
+    if (!ctx || !d_status || (n && (!d_rows || !d_offsets)) || (!n && !d_offsets)) {
+        set_error("invalid argument");
+        return MBRWT_ERR_INVALID;
+    }
+    Ctx &c = *C(ctx);
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (!rows16_supported(c)) return MBRWT_ERR_UNSUPPORTED;
+    WsFence fence_(c.fence, s);
+    try {
+        if (hipSetDevice(c.device) != hipSuccess) return hip_fail(hipGetLastError(), "hipSetDevice");
+        if (c.rows.ready && c.kernel_variant == 0 && n > 0)
+            return rows_get_rows(c, d_rows, n, d_offsets, d_cols, d_cols ? cols_cap : 0, nullptr, s, d_status, 2);
+        // other images: the synchronous call, then its status on the stream
+        uint64_t need = 0;
+        const int rc = run_get_rows16(c, d_rows, n, d_offsets, d_cols, d_cols ? cols_cap : 0, &need, s);
+        if (rc != MBRWT_OK && rc != MBRWT_ERR_CAPACITY && rc != MBRWT_ERR_RANGE) return rc;
+        return rows_set_status(d_status, need, rc, s);
+    } catch (...) {
+        set_error("unexpected exception in mbrwt_get_rows16_device_async");
+        return MBRWT_ERR_INVALID;
+    }
+}
+
+int mbrwt_get_rows16(mbrwt_ctx *ctx, const uint64_t *rows, uint64_t n, uint64_t *offsets, uint16_t *cols,
+                     uint64_t cols_cap, uint64_t *cols_needed) {
+    if (!ctx || !offsets || (n && !rows)) {
+        set_error("invalid argument");
+        return MBRWT_ERR_INVALID;
+    }
+    Ctx &c = *C(ctx);
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (!rows16_supported(c)) return MBRWT_ERR_UNSUPPORTED;
+    WsFence fence_(c.fence, c.stream);
+    try {
+        MBRWT_HIP(hipSetDevice(c.device));
+        return host_get_rows(c, rows, n, offsets, cols, cols ? cols_cap : 0, cols_needed, 2);
+    } catch (...) {
+        set_error("unexpected exception in mbrwt_get_rows16");
         return MBRWT_ERR_INVALID;
     }
 }

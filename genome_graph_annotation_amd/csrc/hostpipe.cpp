@@ -227,20 +227,23 @@ static int grow_pinned(void *&h, size_t &have, size_t bytes) {
 
 // the query of one chunk on the context's stream: the asynchronous row-record
 // call where it exists, else the synchronous call and its status block
-static int enqueue_query(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_off, uint32_t *d_cols, uint64_t cap,
-                         uint64_t *d_status, hipStream_t s) {
+// (width: bytes per label of d_cols, 4 or 2; cap in labels)
+static int enqueue_query(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_off, void *d_cols, uint64_t cap,
+                         uint64_t *d_status, hipStream_t s, uint32_t width) {
     MBRWT_HIP(hipMemsetAsync(d_status, 0, 3 * sizeof(uint64_t), s));
     if (c.rows.ready && c.kernel_variant == 0 && n > 0)
-        return rows_get_rows(c, d_rows, n, d_off, d_cols, cap, nullptr, s, d_status);
+        return rows_get_rows(c, d_rows, n, d_off, d_cols, cap, nullptr, s, d_status, width);
     uint64_t need = 0;
-    const int rc = run_get_rows(c, d_rows, n, d_off, d_cols, cap, &need, s);
+    const int rc = width == 2 ? run_get_rows16(c, d_rows, n, d_off, static_cast<uint16_t *>(d_cols), cap, &need, s)
+                              : run_get_rows(c, d_rows, n, d_off, static_cast<uint32_t *>(d_cols), cap, &need, s);
     if (rc != MBRWT_OK && rc != MBRWT_ERR_CAPACITY && rc != MBRWT_ERR_RANGE) return rc;
     return rows_set_status(d_status, need, rc, s);
 }
 
-int host_get_rows(Ctx &c, const uint64_t *rows, uint64_t n, uint64_t *offsets, uint32_t *cols, uint64_t cols_cap,
-                  uint64_t *cols_needed) {
+int host_get_rows(Ctx &c, const uint64_t *rows, uint64_t n, uint64_t *offsets, void *cols, uint64_t cols_cap,
+                  uint64_t *cols_needed, uint32_t width) {
     int rc;
+    char *const cols_b = static_cast<char *>(cols);  // label i at cols_b + i * width
     if ((rc = pipe_init(c))) return rc;
     HostPipe &P = *c.pipe;
     const hipStream_t sq = c.stream;
@@ -279,7 +282,7 @@ int host_get_rows(Ctx &c, const uint64_t *rows, uint64_t n, uint64_t *offsets, u
         const uint64_t lcap = (uint64_t)((double)s.n * mean * 1.25) + 65536;
         int r;
         if ((r = ensure(s.rows, std::max<uint64_t>(1, s.n) * 8)) || (r = ensure(s.off, (s.n + 1) * 8)) ||
-            (r = ensure(s.cols, lcap * 4)))
+            (r = ensure(s.cols, lcap * width)))
             return r;
         const uint64_t *src = rows + s.row0;
         if (!pin_rows && s.n) {
@@ -297,7 +300,7 @@ int host_get_rows(Ctx &c, const uint64_t *rows, uint64_t n, uint64_t *offsets, u
         MBRWT_HIP(hipStreamWaitEvent(sq, s.ev_in, 0));
         MBRWT_HIP(hipStreamWaitEvent(sq, s.ev_out, 0));
         if ((r = enqueue_query(c, static_cast<uint64_t *>(s.rows.buf), s.n, static_cast<uint64_t *>(s.off.buf),
-                               static_cast<uint32_t *>(s.cols.buf), s.cols.bytes / 4, s.d_status, sq)))
+                               s.cols.buf, s.cols.bytes / width, s.d_status, sq, width)))
             return r;
         MBRWT_HIP(hipMemcpyAsync(s.h_status, s.d_status, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, sq));
         MBRWT_HIP(hipEventRecord(s.ev_q, sq));
@@ -311,9 +314,9 @@ int host_get_rows(Ctx &c, const uint64_t *rows, uint64_t n, uint64_t *offsets, u
         uint64_t need = s.h_status[0], st = s.h_status[1];
         if (st == MBRWT_ERR_CAPACITY) {  // a chunk denser than the slot's estimate: again, with room
             int r;
-            if ((r = ensure(s.cols, need * 4 + 4096))) return r;
+            if ((r = ensure(s.cols, need * width + 4096))) return r;
             if ((r = enqueue_query(c, static_cast<uint64_t *>(s.rows.buf), s.n, static_cast<uint64_t *>(s.off.buf),
-                                   static_cast<uint32_t *>(s.cols.buf), s.cols.bytes / 4, s.d_status, sq)))
+                                   s.cols.buf, s.cols.bytes / width, s.d_status, sq, width)))
                 return r;
             MBRWT_HIP(hipMemcpyAsync(s.h_status, s.d_status, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, sq));
             MBRWT_HIP(hipEventRecord(s.ev_q, sq));
@@ -356,11 +359,12 @@ int host_get_rows(Ctx &c, const uint64_t *rows, uint64_t n, uint64_t *offsets, u
         }
         if (s.copy_cols && need) {
             if (pin_cols) {
-                MBRWT_HIP(hipMemcpyAsync(cols + s.base, s.cols.buf, need * 4, hipMemcpyDeviceToHost, P.s_out));
+                MBRWT_HIP(hipMemcpyAsync(cols_b + s.base * width, s.cols.buf, need * width, hipMemcpyDeviceToHost,
+                                         P.s_out));
             } else {
                 int r;
-                if ((r = grow_pinned(s.h_cols, s.h_cols_bytes, need * 4))) return r;
-                MBRWT_HIP(hipMemcpyAsync(s.h_cols, s.cols.buf, need * 4, hipMemcpyDeviceToHost, P.s_out));
+                if ((r = grow_pinned(s.h_cols, s.h_cols_bytes, need * width))) return r;
+                MBRWT_HIP(hipMemcpyAsync(s.h_cols, s.cols.buf, need * width, hipMemcpyDeviceToHost, P.s_out));
             }
         }
         MBRWT_HIP(hipEventRecord(s.ev_out, P.s_out));
@@ -375,7 +379,7 @@ int host_get_rows(Ctx &c, const uint64_t *rows, uint64_t n, uint64_t *offsets, u
         const uint64_t last = (i + 1 == nch) ? 1 : 0;
         if (!pin_off && s.n + last) parallel_copy(*P.pool, offsets + s.row0, s.h_off, (s.n + last) * 8);
         if (s.copy_cols && !pin_cols && s.need) {
-            parallel_copy(*P.pool, cols + s.base, s.h_cols, s.need * 4);
+            parallel_copy(*P.pool, cols_b + s.base * width, s.h_cols, s.need * width);
         }
         return MBRWT_OK;
     };

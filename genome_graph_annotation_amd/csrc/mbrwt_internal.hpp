@@ -386,6 +386,7 @@ struct Ctx {
     Workspace ws_temp, ws_counts, ws_ovf, ws_scan, ws_rows, ws_out, ws_sort;
     Workspace ws_cls_off, ws_cls_cols;  // get_labels batch: the rows' CSR
     Workspace ws_class;                 // record classes: the batch's classes (rows_class.hip)
+    Workspace ws_cols16;                // mbrwt_get_rows16* without row records: the u32 labels before narrowing
     uint64_t *h_scalars = nullptr;      // pinned: [0] total, [1] overflow count, [2] error
     uint64_t *d_scalars = nullptr;      // device twin
     HostPipe *pipe = nullptr;           // streams, slots and staging of mbrwt_get_rows (lazily created)
@@ -467,8 +468,10 @@ inline unsigned grid256(uint64_t items) {
 // row-record queries (rows.hip)
 // d_status != null: asynchronous (no host synchronisation; the call's
 // {labels needed, status, sticky status bits} land in d_status on the stream)
-int rows_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, uint32_t *d_cols, uint64_t cap,
-                  uint64_t *needed, hipStream_t s, uint64_t *d_status = nullptr);
+// width: bytes per label of d_cols, 4 (u32) or 2 (u16, contexts of at most
+// 65,536 columns: the caller checks); cap counts labels
+int rows_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, void *d_cols, uint64_t cap,
+                  uint64_t *needed, hipStream_t s, uint64_t *d_status = nullptr, uint32_t width = 4);
 // {need, rc, sticky |= 1 << rc} into a caller's status block on the stream
 int rows_set_status(uint64_t *d_status, uint64_t need, int rc, hipStream_t s);
 int rows_get_batch(Ctx &c, const uint64_t *d_rows, const uint64_t *d_cols, uint64_t n, uint8_t *d_out, hipStream_t s);
@@ -493,8 +496,8 @@ int var_measure_range(RowsImage &im, const Ctx &range, VarScratch &ws, uint64_t 
 bool var_lds_fits(const RowsImage &im, double labels_per_row, double record_bytes_per_row);
 int var_build_range(RowsImage &im, const Ctx &range, uint64_t row0, VarScratch &ws, hipStream_t s);
 void var_free_scratch(VarScratch &ws);
-int var_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, uint32_t *d_cols, uint64_t cap,
-                 uint64_t *needed, hipStream_t s, uint64_t *d_status);
+int var_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, void *d_cols, uint64_t cap,
+                 uint64_t *needed, hipStream_t s, uint64_t *d_status, uint32_t width = 4);
 int var_get_batch(Ctx &c, const uint64_t *d_rows, const uint64_t *d_cols, uint64_t n, uint8_t *d_out, hipStream_t s);
 // count_labels (d_counts != null) or the V / L accounting (d_counts == null)
 int var_count(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_counts, uint64_t *visits, uint64_t *labels,
@@ -615,10 +618,17 @@ int run_get_column(Ctx &c, uint64_t column, uint64_t *d_rows, uint64_t rows_cap,
                    hipStream_t s);
 const char *traverse_kernel_name(const Ctx &c);  // the kernel mbrwt_get_rows* launches
 // mbrwt_get_rows: host row ids -> host CSR, chunked and pipelined (hostpipe.cpp)
-int host_get_rows(Ctx &c, const uint64_t *rows, uint64_t n, uint64_t *offsets, uint32_t *cols, uint64_t cols_cap,
-                  uint64_t *cols_needed);
+// (width: bytes per label of cols, 4 or 2)
+int host_get_rows(Ctx &c, const uint64_t *rows, uint64_t n, uint64_t *offsets, void *cols, uint64_t cols_cap,
+                  uint64_t *cols_needed, uint32_t width = 4);
 int run_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, uint32_t *d_cols, uint64_t cap,
                  uint64_t *needed, hipStream_t s);
+// u16 labels (mbrwt_get_rows16*): the row records' own narrow stores, else
+// run_get_rows into ws_cols16 and one narrowing kernel; false + message for
+// a context of more than 65,536 columns
+bool rows16_supported(const Ctx &c);
+int run_get_rows16(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, uint16_t *d_cols, uint64_t cap,
+                   uint64_t *needed, hipStream_t s);
 int run_get_batch(Ctx &c, const uint64_t *d_rows, const uint64_t *d_cols, uint64_t n, uint8_t *d_out, hipStream_t s);
 int run_count_labels(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_counts, hipStream_t s);
 // batched get_labels(indices, presence_ratio) (classify.hip)

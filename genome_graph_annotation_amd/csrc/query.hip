@@ -2383,6 +2383,60 @@ int run_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets
     return MBRWT_OK;
 }
 
+// u16 labels ------------------------------------------------------------
+namespace {
+// (n <= cap: checked by the caller, so no element at or past cap is written)
+__global__ __launch_bounds__(256) void k_narrow_cols(const uint32_t *src, uint16_t *dst, uint64_t n) {
+    const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gs)
+        gst(dst + i, (uint16_t)gld(src + i));
+}
+}  // namespace
+
+bool rows16_supported(const Ctx &c) {
+    if (c.tree.num_columns <= 0x10000u) return true;
+    set_error("u16 labels need a context of at most 65536 columns (this one has " +
+              std::to_string(c.tree.num_columns) + ")");
+    return false;
+}
+
+// Row records store u16 themselves (k_compact_tiles / k_var_decode).  Every
+// other image (node layouts, row shards, a forced kernel variant) answers
+// through its u32 path into ws_cols16 -- grown from the call's own total, as
+// classify_batch grows its CSR, never sized by the caller's capacity -- and
+// one narrowing pass into the caller's buffer: the u32 call's time plus 6
+// bytes of traffic per label.
+int run_get_rows16(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, uint16_t *d_cols, uint64_t cap,
+                   uint64_t *needed, hipStream_t s) {
+    if (c.rows.ready && c.kernel_variant == 0)
+        return rows_get_rows(c, d_rows, n, d_offsets, d_cols, cap, needed, s, nullptr, 2);
+    uint64_t need = 0;
+    int rc;
+    if (!d_cols || !cap) {  // count only
+        rc = run_get_rows(c, d_rows, n, d_offsets, nullptr, 0, &need, s);
+    } else {
+        rc = run_get_rows(c, d_rows, n, d_offsets, reinterpret_cast<uint32_t *>(c.ws_cols16.buf),
+                          c.ws_cols16.bytes / sizeof(uint32_t), &need, s);
+        if (rc == MBRWT_ERR_CAPACITY && need <= cap) {
+            if ((rc = ensure(c.ws_cols16, (need + need / 8 + 1024) * sizeof(uint32_t)))) return rc;
+            rc = run_get_rows(c, d_rows, n, d_offsets, reinterpret_cast<uint32_t *>(c.ws_cols16.buf),
+                              c.ws_cols16.bytes / sizeof(uint32_t), &need, s);
+        }
+    }
+    if (needed) *needed = need;
+    if (rc) return rc;
+    if (need > cap) {  // (the workspace held what the caller's buffer does not)
+        set_error("cols_cap too small");
+        return MBRWT_ERR_CAPACITY;
+    }
+    if (need) {
+        hipLaunchKernelGGL(k_narrow_cols, dim3(grid256(need)), dim3(256), 0, s,
+                           reinterpret_cast<const uint32_t *>(c.ws_cols16.buf), d_cols, need);
+        MBRWT_HIP(hipGetLastError());
+    }
+    return MBRWT_OK;
+}
+
 int run_count_work(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *visits, uint64_t *labels, hipStream_t s) {
     if (c.nodes_freed) return rows_count_work(c, d_rows, n, visits, labels, s);
     if (!c.shards.empty()) return sharded_count_work(c, d_rows, n, visits, labels, s);

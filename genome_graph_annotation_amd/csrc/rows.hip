@@ -813,7 +813,7 @@ struct CompactParams {
     const uint32_t *tile_counts;
     const uint64_t *tile_offsets;
     uint64_t *offsets;
-    uint32_t *cols;
+    void *cols;                   // the CSR's labels: u32, or u16 (k_compact_tiles<WIDE, uint16_t>)
     uint64_t n, cap;
     unsigned long long *scalars;  // the traversal's counters ([2] error flags)
     unsigned long long *status;   // {total, status, sticky}
@@ -824,7 +824,11 @@ struct CompactParams {
     const uint32_t *table;        // RWT (direct tiles)
     uint32_t stk_lim;             // walk stack frames (the tree's height; dynamic LDS)
 };
-template <bool WIDE>
+// OUT = uint16_t (mbrwt_get_rows16*): the same labels stored as they lie in
+// the region, one u16 per lane and store -- a tile's offset has any parity,
+// so its destination is aligned to 2 bytes only, and a wider store at either
+// end would reach into the neighbouring tile, which another wave writes.
+template <bool WIDE, class OUT>
 __global__ __launch_bounds__(256) void k_compact_tiles(CompactParams p) {
     extern __shared__ uint32_t cstk[];  // the direct walks' stacks: 4 x 128 x stk_lim words (two per lane and frame)
     const uint64_t n = p.n;
@@ -872,11 +876,11 @@ __global__ __launch_bounds__(256) void k_compact_tiles(CompactParams p) {
         const uint64_t tb = base[k];
         base[k] = rbase;  // (the walks below: each row's own offset)
         if (tc[k] >> 31) continue;  // a direct tile: walked below, once the copies' registers are free
-        uint32_t *dst = p.cols + tb;
+        OUT *dst = static_cast<OUT *>(p.cols) + tb;
 #pragma unroll
         for (uint32_t j = 0; j < 8; ++j) {
             const uint32_t i = lane + 64 * j;
-            if (i < tot) gst(dst + i, v[k][j]);
+            if (i < tot) gst(dst + i, (OUT)v[k][j]);
         }
         const uint16_t *lab = reinterpret_cast<const uint16_t *>(p.temp + t * (uint64_t)region + 128);
         for (uint32_t i0 = 512; i0 < tot; i0 += 512) {
@@ -889,7 +893,7 @@ __global__ __launch_bounds__(256) void k_compact_tiles(CompactParams p) {
 #pragma unroll
             for (uint32_t j = 0; j < 8; ++j) {
                 const uint32_t i = i0 + lane + 64 * j;
-                if (i < tot) gst(dst + i, w[j]);
+                if (i < tot) gst(dst + i, (OUT)w[j]);
             }
         }
     }
@@ -911,10 +915,10 @@ __global__ __launch_bounds__(256) void k_compact_tiles(CompactParams p) {
             uint64_t masks;
             uint32_t count;
             rows_locate(p.v, row, masks, count);  // (count = cnt: rows out of range have none)
-            uint32_t *dst = p.cols + base[k];
+            OUT *dst = static_cast<OUT *>(p.cols) + base[k];
             uint32_t j = 0;
             auto put = [&](uint32_t col) {
-                if (j < count) gst(dst + j, col);
+                if (j < count) gst(dst + j, (OUT)col);
                 ++j;
             };
             auto byte = [&](uint32_t o) { return (uint32_t)gld_at<uint8_t>(masks + o); };
@@ -1110,8 +1114,8 @@ static uint32_t rows_walk_of(const Ctx &c) {
     return im.mask1 ? WALK_MASK1 : WALK_GENERAL;
 }
 
-int rows_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, uint32_t *d_cols, uint64_t cap,
-                  uint64_t *needed, hipStream_t s, uint64_t *d_status) {
+int rows_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, void *d_cols, uint64_t cap,
+                  uint64_t *needed, hipStream_t s, uint64_t *d_status, uint32_t width) {
     const RowsImage &im = c.rows;
     if (n == 0 && d_status) return MBRWT_ERR_UNSUPPORTED;  // (the caller's generic path handles it)
     if (n == 0) {
@@ -1120,7 +1124,7 @@ int rows_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offset
         if (needed) *needed = 0;
         return MBRWT_OK;
     }
-    if (im.var) return var_get_rows(c, d_rows, n, d_offsets, d_cols, cap, needed, s, d_status);
+    if (im.var) return var_get_rows(c, d_rows, n, d_offsets, d_cols, cap, needed, s, d_status, width);
     if (n > 0x7FFFFFF0ull) {
         set_error("batch larger than 2^31 rows");
         return MBRWT_ERR_UNSUPPORTED;
@@ -1243,11 +1247,12 @@ int rows_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offset
             MBRWT_HIP(hipStreamWaitEvent(c.s_compact, c.ev_trav, 0));
             sc = c.s_compact;
         }
-        if (im.max_arity > 16)
-            hipLaunchKernelGGL(k_compact_tiles<true>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, sc, cp);
-        else
-            hipLaunchKernelGGL(k_compact_tiles<false>, dim3((unsigned)((waves + 3) / 4)), dim3(256),
-                               (size_t)256 * cp.stk_lim * 8, sc, cp);
+        using CompactFn = void (*)(CompactParams);
+        const bool wide = im.max_arity > 16, narrow = width == 2;
+        const CompactFn cfn = wide ? (narrow ? k_compact_tiles<true, uint16_t> : k_compact_tiles<true, uint32_t>)
+                                   : (narrow ? k_compact_tiles<false, uint16_t> : k_compact_tiles<false, uint32_t>);
+        hipLaunchKernelGGL(cfn, dim3((unsigned)((waves + 3) / 4)), dim3(256),
+                           wide ? (size_t)0 : (size_t)256 * cp.stk_lim * 8, sc, cp);
         MBRWT_HIP(hipGetLastError());
         if (sc != s) {
             MBRWT_HIP(hipEventRecord(c.ev_comp, sc));

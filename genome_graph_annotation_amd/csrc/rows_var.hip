@@ -377,7 +377,7 @@ struct VarParams {
     uint64_t *loc;                // per batch row: record address | length in 4-byte units << 48
     uint32_t *cnt;                // per batch row: label count (n + 1 entries; cnt[n] = 0)
     const uint64_t *offsets;      // the CSR offsets (the scan of cnt)
-    uint32_t *cols;
+    void *cols;                   // the CSR's labels: u32, or u16 (k_var_decode<G, WPB, uint16_t>)
     uint64_t cap;
     const uint32_t *units;        // per unit: first column | arity << 16
     uint32_t U;
@@ -414,7 +414,14 @@ __global__ __launch_bounds__(256) void k_var_locate(VarParams p) {
 // (G >= 8: tiles of <= 8 rows need < 6 KB of LDS per wave, so 24 waves per
 // CU fit when the registers do: 6 waves per SIMD requested, 79 VGPRs, no
 // scratch; G <= 4 is bound by LDS at 16 waves per CU anyway.)
-template <int G, int WPB>
+// OUT = uint16_t (mbrwt_get_rows16*): the tile's destination is aligned to 2
+// bytes only, so the tile is staged `sh` labels into the stage, sh = the
+// destination's distance in labels from the 16-byte boundary before it: stage
+// and destination then share their phase, whole groups of 8 labels leave as
+// one aligned 16-byte LDS read and one aligned 16-byte store, and the partial
+// groups at the tile's two ends as u16 stores -- no store reaches a label of
+// a neighbouring tile, which another wave writes.
+template <int G, int WPB, class OUT>
 __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(G >= 8 ? 6 : 1))) void k_var_decode(VarParams p) {
     constexpr uint32_t R = 64 / G;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_var[];
@@ -469,7 +476,10 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(G >= 8
         const uint32_t TC = __builtin_amdgcn_readlane(x, 63);
         const uint32_t cs = x - nch;  // this row's first chunk (valid on lane q == 0)
         const uint32_t cs_row = (uint32_t)__shfl((int)cs, (int)(rr * G), 64);
-        const bool fits = TC * 16 <= p.CR && ttot <= p.CS;
+        uint32_t sh = 0;
+        if constexpr (sizeof(OUT) == 2)
+            sh = __builtin_amdgcn_readfirstlane((uint32_t)(((uint64_t)(uintptr_t)p.cols >> 1) + tbase) & 7u);
+        const bool fits = TC * 16 <= p.CR && ttot + sh <= p.CS;
         if (fits) {
             for (uint32_t k = 0; k < nch; ++k) owner[cs + k] = (uint8_t)rr;
             wave_sync();
@@ -555,42 +565,59 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(G >= 8
         const uint32_t pos = (uint32_t)(roff - tbase) + lb;  // the lane's first label in the tile
         if (fits) {
             const uint32_t us = p.ustride;
+            const uint32_t spos = pos + sh;  // ... in the stage
             // (r05: mask bytes read as words and labels stored in pairs halved
             // the LDS bank-conflict cycles, 218 M -> 108 M per 10 M rows, but
             // added 17 % VALU: 2.46 against 2.22 ms; profiles/r05/v06_*)
             if (us && !(us & (us - 1))) {  // (a shift: v_mul_lo_u32 issues at a quarter rate)
                 const uint32_t sh = (uint32_t)__builtin_ctz(us);
                 var_lane_labels(word_l, byte_l, wi, wv0, 4 * W + j0, labs, [&](uint32_t u) -> uint32_t { return u << sh; },
-                                [&](uint32_t k, uint32_t lab) { stage[pos + k] = (uint16_t)lab; });
+                                [&](uint32_t k, uint32_t lab) { stage[spos + k] = (uint16_t)lab; });
             } else if (us)
                 var_lane_labels(word_l, byte_l, wi, wv0, 4 * W + j0, labs, [&](uint32_t u) -> uint32_t { return u * us; },
-                                [&](uint32_t k, uint32_t lab) { stage[pos + k] = (uint16_t)lab; });
+                                [&](uint32_t k, uint32_t lab) { stage[spos + k] = (uint16_t)lab; });
             else
                 var_lane_labels(word_l, byte_l, wi, wv0, 4 * W + j0, labs,
                                 [&](uint32_t u) -> uint32_t { return ubase[u]; },
-                                [&](uint32_t k, uint32_t lab) { stage[pos + k] = (uint16_t)lab; });
+                                [&](uint32_t k, uint32_t lab) { stage[spos + k] = (uint16_t)lab; });
             wave_sync();
-            // the tile's labels: contiguous in the CSR, 4 per lane and store
-            uint32_t *dst = p.cols + tbase;
-            for (uint32_t i = 4 * lane; i < ttot; i += 256) {
-                if (i + 4 <= ttot) {
-                    // one 8-byte LDS read per 4 labels (r05: the same LDS instruction
-                    // count and conflicts as four u16 reads -- the compiler merged
-                    // those already -- 2.150 vs 2.155 ms, profiles/r05/v11_*)
-                    const uint64_t w4 = *(const AS_LDS uint64_t *)(stage + i);
-                    const uint32_t lo = (uint32_t)w4, hi = (uint32_t)(w4 >> 32);
-                    *(AS_GLOBAL u32x4_t *)(uintptr_t)(dst + i) = u32x4_t{lo & 0xFFFFu, lo >> 16, hi & 0xFFFFu, hi >> 16};
-                } else {
-                    for (uint32_t j = i; j < ttot; ++j) gst(dst + j, (uint32_t)stage[j]);
+            // the tile's labels: contiguous in the CSR, 16 bytes per lane and store
+            // (u16: 8 labels, u32: 4)
+            if constexpr (sizeof(OUT) == 2) {
+                // stage label e lies at dst[e]: dst + e is 16-byte aligned where e % 8 == 0
+                uint16_t *dst = static_cast<uint16_t *>(p.cols) + tbase - sh;
+                const uint32_t e1 = sh + ttot;
+                for (uint32_t e = 8 * lane; e < e1; e += 512) {
+                    if (e >= sh && e + 8 <= e1) {
+                        *(AS_GLOBAL u32x4_t *)(uintptr_t)(dst + e) = *(const AS_LDS u32x4_t *)(stage + e);
+                    } else {
+                        const uint32_t a = e < sh ? sh : e, b = e + 8 < e1 ? e + 8 : e1;
+                        for (uint32_t j = a; j < b; ++j) gst(dst + j, (uint16_t)stage[j]);
+                    }
+                }
+            } else {
+                uint32_t *dst = static_cast<uint32_t *>(p.cols) + tbase;
+                for (uint32_t i = 4 * lane; i < ttot; i += 256) {
+                    if (i + 4 <= ttot) {
+                        // one 8-byte LDS read per 4 labels (r05: the same LDS instruction
+                        // count and conflicts as four u16 reads -- the compiler merged
+                        // those already -- 2.150 vs 2.155 ms, profiles/r05/v11_*)
+                        const uint64_t w4 = *(const AS_LDS uint64_t *)(stage + i);
+                        const uint32_t lo = (uint32_t)w4, hi = (uint32_t)(w4 >> 32);
+                        *(AS_GLOBAL u32x4_t *)(uintptr_t)(dst + i) =
+                            u32x4_t{lo & 0xFFFFu, lo >> 16, hi & 0xFFFFu, hi >> 16};
+                    } else {
+                        for (uint32_t j = i; j < ttot; ++j) gst(dst + j, (uint32_t)stage[j]);
+                    }
                 }
             }
             wave_sync();  // the stage, the chunks and the owners are reused
         } else {
             // a tile beyond the LDS budget: records read and labels stored
             // straight from / to global memory
-            uint32_t *dst = p.cols + tbase + pos;
+            OUT *dst = static_cast<OUT *>(p.cols) + tbase + pos;
             var_lane_labels(word_g, byte_g, wi, wv0, 4 * W + j0, labs, [&](uint32_t u) -> uint32_t { return ubase[u]; },
-                            [&](uint32_t k, uint32_t lab) { gst(dst + k, lab); });
+                            [&](uint32_t k, uint32_t lab) { gst(dst + k, (OUT)lab); });
         }
     }
 }
@@ -699,12 +726,13 @@ VarView var_view(const Ctx &c) {
 
 using VarFn = void (*)(VarParams);
 constexpr uint32_t kVarWpb = 4;
+template <class OUT>
 VarFn var_fn(uint32_t G) {
-    return G == 1    ? k_var_decode<1, kVarWpb>
-           : G == 2  ? k_var_decode<2, kVarWpb>
-           : G == 4  ? k_var_decode<4, kVarWpb>
-           : G == 8  ? k_var_decode<8, kVarWpb>
-                     : k_var_decode<16, kVarWpb>;
+    return G == 1    ? k_var_decode<1, kVarWpb, OUT>
+           : G == 2  ? k_var_decode<2, kVarWpb, OUT>
+           : G == 4  ? k_var_decode<4, kVarWpb, OUT>
+           : G == 8  ? k_var_decode<8, kVarWpb, OUT>
+                     : k_var_decode<16, kVarWpb, OUT>;
 }
 
 }  // namespace
@@ -759,8 +787,8 @@ bool var_lds_fits(const RowsImage &im, double labels_per_row, double record_byte
     return var_geometry_of(im.var_G, (uint32_t)im.var_units.size(), labels_per_row, record_bytes_per_row).lds_ok;
 }
 
-int var_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, uint32_t *d_cols, uint64_t cap,
-                 uint64_t *needed, hipStream_t s, uint64_t *d_status) {
+int var_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, void *d_cols, uint64_t cap,
+                 uint64_t *needed, hipStream_t s, uint64_t *d_status, uint32_t width) {
     const RowsImage &im = c.rows;
     if (n > 0x7FFFFFF0ull) {
         set_error("batch larger than 2^31 rows");
@@ -804,7 +832,7 @@ int var_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets
     p.ustride = im.var_ustride;
     p.scalars = d_sc;
     p.status = st_blk;
-    const VarFn kfn = var_fn(G);
+    const VarFn kfn = width == 2 ? var_fn<uint16_t>(G) : var_fn<uint32_t>(G);
     const size_t lds = ((p.U + 32) * 2 + 15) / 16 * 16 + kVarWpb * (size_t)(CR + CR / 16 + 2 * CS);
     const uint32_t threads = 64 * kVarWpb;
     uint64_t resident = 0;  // (capped only by MBRWT_BUILD_ROWS_WGS_PER_CU)

@@ -435,6 +435,29 @@ int mbrwt_get_rows_device(mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n, ui
 int mbrwt_get_rows_device_async(mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets,
                                 uint32_t *d_cols, uint64_t cols_cap, uint64_t *d_status, void *stream);
 
+/*
+ * The three calls above with 16-bit labels: cols / d_cols holds uint16_t and
+ * cols_cap / cols_needed count uint16_t elements; offsets, label order, the
+ * capacity protocol, the NULL-cols count-only call and the status block are
+ * those of the u32 calls.  For contexts of at most 65,536 columns (exactly
+ * 65,536 is allowed: label 65,535 is a value, not a sentinel); a context of
+ * more answers MBRWT_ERR_UNSUPPORTED before any launch, with the column count
+ * in mbrwt_last_error_message.  Alignment: d_cols must be aligned to 2 bytes,
+ * nothing more (a slice at an odd element offset of a larger buffer is fine).
+ * Row-record contexts store the narrow labels in their last kernel (half the
+ * label bytes written, and half downloaded by the host call); every other
+ * context (per-node images, row shards, a forced MBRWT_OPT_KERNEL variant)
+ * runs its u32 query into a context workspace of 4 bytes per label and
+ * narrows into the caller's buffer, so there the call costs the u32 call
+ * plus one pass over the labels.
+ */
+int mbrwt_get_rows16(mbrwt_ctx *ctx, const uint64_t *rows, uint64_t n, uint64_t *offsets, uint16_t *cols,
+                     uint64_t cols_cap, uint64_t *cols_needed);
+int mbrwt_get_rows16_device(mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets,
+                            uint16_t *d_cols, uint64_t cols_cap, uint64_t *cols_needed, void *stream);
+int mbrwt_get_rows16_device_async(mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets,
+                                  uint16_t *d_cols, uint64_t cols_cap, uint64_t *d_status, void *stream);
+
 /* Batched BRWT::get (BRWT.cpp:9-24): out[i] = bit (rows[i], cols[i]). Host buffers. */
 int mbrwt_get_batch(mbrwt_ctx *ctx, const uint64_t *rows, const uint64_t *cols, uint64_t n, uint8_t *out);
 int mbrwt_get_batch_device(mbrwt_ctx *ctx, const uint64_t *d_rows, const uint64_t *d_cols, uint64_t n,
