@@ -213,6 +213,7 @@ SIGNATURES = {
     "mbrwt_strerror": (C.c_char_p, [C.c_int]),
     "mbrwt_last_error_message": (C.c_char_p, []),
     "mbrwt_traverse_kernel": (C.c_char_p, [C.c_void_p]),
+    "mbrwt_overflow_rows": (C.c_uint64, [C.c_void_p]),
     # include/mbrwt_wt.h (BinRel-WT)
     "mbrwt_wt_create": (C.c_int, [C.POINTER(BinRelDesc), C.c_int, C.POINTER(C.c_void_p)]),
     "mbrwt_wt_create_synthetic": (C.c_int, [C.POINTER(BinRelSynthDesc), C.c_int, C.POINTER(C.c_void_p)]),

@@ -535,6 +535,10 @@ class BRWTDevice:
         """Name of the traversal kernel get_rows launches (diagnostics)."""
         return (L.lib().mbrwt_traverse_kernel(self._h) or b"").decode()
 
+    def overflow_rows(self) -> int:
+        """Rows the last get_rows*_device* call on the node images left to its direct pass (diagnostics)."""
+        return int(L.lib().mbrwt_overflow_rows(self._h))
+
     def take_timing(self):
         ms = C.c_double(0)
         k = C.c_uint64(0)

@@ -1213,4 +1213,11 @@ const char *mbrwt_traverse_kernel(mbrwt_ctx *ctx) {
     return traverse_kernel_name(c.shards.empty() ? c : *c.shards[0]);
 }
 
+uint64_t mbrwt_overflow_rows(mbrwt_ctx *ctx) {
+    if (!ctx) return 0;
+    Ctx &c = *C(ctx);
+    std::lock_guard<std::mutex> lk(c.mu);
+    return c.overflow_rows;
+}
+
 }  // extern "C"

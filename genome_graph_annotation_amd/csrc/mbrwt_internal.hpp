@@ -406,6 +406,7 @@ struct Ctx {
     hipEvent_t ev_trav = nullptr, ev_comp = nullptr;
     double timing_ms = 0;
     uint64_t timing_launches = 0;
+    uint64_t overflow_rows = 0;  // rows the last node-image get_rows left to the direct pass (mbrwt_overflow_rows)
     // launch geometry of the last rowblock kernel (resident_workgroups): the
     // occupancy query and the LDS attribute are host calls paid once, not per batch
     const void *rb_fn = nullptr;

@@ -788,7 +788,9 @@ __global__ __launch_bounds__(256, 8) void k_traverse_fast2(TravParams p) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const uint32_t lim = cnt < kStageLabels ? cnt : kStageLabels;
+            // a row of more than K labels stores nothing (the direct pass writes
+            // it): with K < kStageLabels its stage would run past the chunk's region
+            const uint32_t lim = cnt > p.K ? 0u : cnt < kStageLabels ? cnt : kStageLabels;
             uint32_t *const dst = slot_ptr();
             for (uint32_t q = c; q < lim; q += 4) gst(dst + q, (uint32_t)stage[q]);
             if (c == 0) {
@@ -1992,7 +1994,11 @@ hipError_t launch(const Ctx &c, const Trav &t, uint64_t n, hipStream_t s, const 
     return hipGetLastError();
 }
 
-// label-map entries the compaction kernels stage in LDS (0: identity or too large)
+// label-map entries the compaction kernels stage in LDS (0: identity or too
+// large).  At kMapLdsMax entries k_compact asks for 64 KiB of dynamic LDS
+// beside its 2,056 static bytes: gfx950 gives a workgroup up to 160 KiB with
+// no function attribute (measured: the launch is accepted and exact,
+// tests/test_gpu_node_edges.py test_label_map_limit).
 uint32_t label_map_lds(const Ctx &c) {
     const size_t m = c.tree.label_perm.size();
     return (c.d_label_map && m <= kMapLdsMax) ? (uint32_t)m : 0u;
@@ -2120,7 +2126,7 @@ int finish_nodes_call(Ctx &c, uint64_t cap, uint64_t *needed, uint64_t *overflow
         return rc;
     }
     const uint64_t total = c.h_scalars[0];
-    *overflow = c.h_scalars[1];
+    *overflow = c.overflow_rows = c.h_scalars[1];
     if (needed) *needed = total;
     if (total > cap) {
         set_error("cols_cap too small");

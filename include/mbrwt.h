@@ -630,6 +630,12 @@ const char *mbrwt_last_error_message(void); /* thread-local detail of the last f
    tree under the current MBRWT_OPT_KERNEL (static string; "" for a null ctx). */
 const char *mbrwt_traverse_kernel(mbrwt_ctx *ctx);
 
+/* Diagnostics: the rows that the last mbrwt_get_rows*_device* call on the
+   per-node images (one batch, no row shards) left to its direct pass -- rows
+   of more labels than their slot, or the 16 rows of a rowblock of more labels
+   than its 16 slots (MBRWT_OPT_SLOT_LABELS).  0 for a null ctx. */
+uint64_t mbrwt_overflow_rows(mbrwt_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,10 @@ closed form of any row id is staircase_count().
 
 The batch builders return row ids of a staircase whose row 0 is empty and
 whose row k <= m has k labels; they place rows of chosen label counts on
-chosen lanes of the 64-row tiles get_rows works in.
+chosen lanes of the 64-row tiles get_rows works in -- or, for the node-image
+kernels, of their 16-row rowblocks, 8-row chunks and 256-row tiles
+(tile_totals(tile=...), node_geometry).  windows() is a low staircase placed
+anywhere in the width (rows of few labels over a deep or a wide tree).
 """
 import numpy as np
 
@@ -55,28 +58,38 @@ def sweep_rows(m):
 _LANE_PAIRS = ((0, 63), (0, 1), (31, 32))
 
 
-def tile_totals(m, lo, hi):
-    """One 64-row tile per total T in [lo, hi]: rows a and T - a on the lanes
-    of _LANE_PAIRS (cycled with T), 62 copies of row 0 around them; a cycles
-    through 1, T // 2 and the largest row that fits.  Where two rows of at
-    most m labels cannot reach T (T > 2 m), full rows (m labels) take the
-    next free lanes until the rest fits two rows; totals beyond 64 m (a tile
-    of full rows) are left out."""
+def lane_pairs(tile):
+    """The lanes of tile_totals' two heavy rows: first and last, the first
+    two, the two around the middle -- (0, 63), (0, 1), (31, 32) at 64;
+    (0, 15), (0, 1), (7, 8) at 16; (0, 7), (0, 1), (3, 4) at 8."""
+    return ((0, tile - 1), (0, 1), (tile // 2 - 1, tile // 2))
+
+
+def tile_totals(m, lo, hi, tile=TILE, lanes=None):
+    """One `tile`-row tile per total T in [lo, hi]: rows a and T - a on the
+    lanes of `lanes` (lane_pairs(tile) by default; cycled with T), tile - 2
+    copies of row 0 around them; a cycles through 1, T // 2 and the largest
+    row that fits.  Where two rows of at most m labels cannot reach T
+    (T > 2 m), full rows (m labels) take the next free lanes until the rest
+    fits two rows; totals beyond tile * m (a tile of full rows) are left out.
+    The node kernels work in 16-row rowblocks, 8-row chunks and 256-row
+    tiles, the row records in 64-row tiles (the default)."""
+    lanes = lane_pairs(tile) if lanes is None else lanes
     tiles = []
-    for i, T in enumerate(range(lo, min(hi, TILE * m) + 1)):
-        tile = np.zeros(TILE, dtype=np.uint64)
-        p0, p1 = _LANE_PAIRS[i % 3]
-        free = [l for l in range(TILE) if l not in (p0, p1)]
+    for i, T in enumerate(range(lo, min(hi, tile * m) + 1)):
+        t = np.zeros(tile, dtype=np.uint64)
+        p0, p1 = lanes[i % len(lanes)]
+        free = [l for l in range(tile) if l not in (p0, p1)]
         rest = T
         while rest > 2 * m:
-            tile[free.pop(0)] = m
+            t[free.pop(0)] = m
             rest -= m
         a = (1, rest // 2, min(m, rest))[(i // 3) % 3]
         a = min(max(a, rest - m, 0), min(m, rest))
-        tile[p0], tile[p1] = a, rest - a
-        assert int(tile.sum()) == T and int(tile.max()) <= m
-        tiles.append(tile)
-    return np.concatenate(tiles)
+        t[p0], t[p1] = a, rest - a
+        assert int(t.sum()) == T and int(t.max()) <= m
+        tiles.append(t)
+    return np.concatenate(tiles) if tiles else np.zeros(0, dtype=np.uint64)
 
 
 def geometry_heavy(m):
@@ -117,8 +130,9 @@ def gather_csr(off, cols, rows):
     return out_off, np.asarray(cols)[start + np.arange(total)]
 
 
-def closed_form_ok(off, cols, counts):
-    """diff(off) == counts and every row's labels, sorted, are range(count)."""
+def closed_form_ok(off, cols, counts, shifts=None):
+    """diff(off) == counts and every row's labels, sorted, are range(count)
+    -- or, with `shifts` (one per row), shift + range(count)."""
     off = np.asarray(off, dtype=np.int64)
     counts = np.asarray(counts, dtype=np.int64)
     if len(off) != len(counts) + 1 or off[0] != 0 or not np.array_equal(np.diff(off), counts):
@@ -129,4 +143,84 @@ def closed_form_ok(off, cols, counts):
     seg = np.repeat(np.arange(len(counts)), counts)
     order = np.lexsort((cols, seg))
     want = np.arange(int(off[-1])) - np.repeat(off[:-1], counts)
+    if shifts is not None:
+        want = want + np.repeat(np.asarray(shifts, dtype=np.int64), counts)
     return np.array_equal(cols[order], want)
+
+
+# ---- the node-image fixtures (csrc/query.hip: 16-row rowblocks, 8-row chunks,
+# 256-row tiles; tests/test_gpu_node_edges.py) ---------------------------------
+
+def windows(m, top, shifts):
+    """bool [len(shifts) * (top + 1), m], a LOW staircase: row i * (top + 1) + k
+    has the columns [shifts[i], shifts[i] + k), k in 0..top.  Rows of at most
+    `top` labels anywhere in the width: at shift 0, across a boundary between
+    two children of the tree's root, up to the last column (shift m - top)."""
+    shifts = np.asarray(shifts, dtype=np.int64)
+    assert top >= 0 and (shifts >= 0).all() and (shifts + top <= m).all()
+    ids = np.arange(len(shifts) * (top + 1))
+    lo = windows_shift(ids, top, shifts)[:, None]
+    c = np.arange(m)[None, :]
+    return (c >= lo) & (c < lo + windows_count(ids, top)[:, None])
+
+
+# (m, top, shifts) over a binary tree of 256 columns: the root's children
+# split the width at column 128, which the rows of shift 112 straddle
+WINDOWS_DEEP = (256, 32, (0, 112, 224))
+WIDE_TOP = 140
+
+
+def windows_wide(m):
+    """(m, top, shifts) of the windows block of label_map_matrix(m)."""
+    return m, WIDE_TOP, (0, m - WIDE_TOP)
+
+
+def label_map_matrix(m):
+    """About 300 rows over m >= 16,384 columns: windows(*windows_wide(m)),
+    then one row each holding the columns 0, 16,383 and m - 1 alone, and one
+    holding all of them."""
+    w = windows(*windows_wide(m))
+    extra = np.zeros((4, m), dtype=bool)
+    for i, c in enumerate((0, 16383, m - 1)):
+        extra[i, c] = extra[3, c] = True
+    return np.concatenate([w, extra])
+
+
+def windows_count(rows, top):
+    """Labels of the rows `rows` of windows(m, top, shifts) (closed form)."""
+    return np.asarray(rows, dtype=np.int64) % (top + 1)
+
+
+def windows_shift(rows, top, shifts):
+    """First column of the rows `rows` of windows(m, top, shifts)."""
+    return np.asarray(shifts, dtype=np.int64)[np.asarray(rows, dtype=np.int64) // (top + 1)]
+
+
+def windows_rows(counts, top, nshifts):
+    """Row ids of windows(m, top, shifts) with the label counts `counts`
+    (each <= top), the shift cycling with the position in the batch."""
+    counts = np.asarray(counts, dtype=np.uint64)
+    assert int(counts.max(initial=0)) <= top
+    return (np.arange(len(counts), dtype=np.uint64) % np.uint64(nshifts)) * np.uint64(top + 1) + counts
+
+
+# partial and full chunks (8), rowblocks (16), row-record tiles (64) and
+# compaction tiles (256); 16 * 7 + 1 and 16 * 28 + 1: one rowblock more than
+# the 7 (k_traverse_ptw) and 4 (k_traverse_p2w) waves of a workgroup take in
+# one and in seven rounds
+NODE_SIZES = (1, 7, 8, 9, 15, 16, 17, 63, 64, 65, 255, 256, 257, 16 * 7 + 1, 16 * 28 + 1)
+
+
+def node_geometry(k, sizes=NODE_SIZES):
+    """geometry() in the node kernels' units: batches of n in `sizes` rows
+    around the heavy row k -- (name, rows) with the heavy row first and last
+    among light rows (0..7 labels), and alone in the middle of empty rows."""
+    out = []
+    for n in sizes:
+        light = (np.arange(n) % 8).astype(np.uint64)
+        first, last, alone = light.copy(), light.copy(), np.zeros(n, dtype=np.uint64)
+        first[0] = k
+        last[n - 1] = k
+        alone[n // 2] = k
+        out += [(f"first-{n}", first), (f"last-{n}", last), (f"alone-{n}", alone)]
+    return out

@@ -206,6 +206,10 @@ def test_staircase_rows(oracle_mod, build_env, name):
     # -- the built form ---------------------------------------------------
     if expect == "nodes":
         assert dev.layout() == "nodes" and st is None
+        # (a full row's record under the 512-column root child is over a record block's 64
+        # bytes, so that child is not packed: no rowblock kernel and no fast2 on this tree.
+        # Their edges are tests/test_gpu_node_edges.py's.)
+        assert dev.traverse_kernel() == "k_traverse_group", dev.traverse_kernel()
     elif expect == "auto":
         # whatever AUTO picks must be exact; dense rows of a uniform tree:
         # the variable-length records (test_auto_layout) or the node images
