@@ -104,6 +104,15 @@ class ColumnsDesc(C.Structure):
     ]
 
 
+class RowsDesc(C.Structure):  # mbrwt_rows_desc: CSR rows (mbrwt_create_from_rows)
+    _fields_ = [
+        ("num_rows", C.c_uint64),
+        ("num_columns", C.c_uint64),
+        ("offsets", u64p),
+        ("cols", u32p),
+    ]
+
+
 class BinRelDesc(C.Structure):  # include/mbrwt_wt.h
     _fields_ = [
         ("num_rows", C.c_uint64),
@@ -131,6 +140,9 @@ SIGNATURES = {
     "mbrwt_create_from_columns": (C.c_int, [C.POINTER(ColumnsDesc), C.c_int, C.POINTER(C.c_void_p)]),
     "mbrwt_create_from_columns_relaxed": (C.c_int, [C.POINTER(ColumnsDesc), C.c_uint64, C.c_int,
                                                     C.POINTER(C.c_void_p)]),
+    "mbrwt_create_from_rows": (C.c_int, [C.POINTER(RowsDesc), C.POINTER(ShapeDesc), C.c_uint32, C.c_int,
+                                         C.POINTER(C.c_void_p)]),
+    "mbrwt_tree_basic_shape": (C.c_int, [C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
     "mbrwt_create_relaxed": (C.c_int, [C.POINTER(TreeDesc), C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]),
     "mbrwt_get_labels_batch": (C.c_int, [C.c_void_p, u64p, C.c_uint64, u64p, C.c_uint64, C.c_double, u64p, u32p,
                                          C.c_uint64, u64p]),

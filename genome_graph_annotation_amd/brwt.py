@@ -168,6 +168,16 @@ def serialize_tree(tree) -> bytes:
     return buf[: need.value].tobytes()
 
 
+def basic_shape(num_columns, arity):
+    """The shape of the basic partitioner's tree of `arity` over num_columns
+    columns (mbrwt_tree_basic_shape; host only): the dict
+    BRWTDevice.synthetic_shaped and BRWTDevice.from_rows take."""
+    h = C.c_void_p()
+    L.check(L.lib().mbrwt_tree_basic_shape(int(num_columns), int(arity), C.byref(h)), "mbrwt_tree_basic_shape")
+    t = _tree_dict(h)
+    return dict(num_children=t["num_children"], first_child=t["first_child"], leaf_column=t["leaf_column"])
+
+
 @contextlib.contextmanager
 def build_layout(layout):
     """Device layout of the contexts created inside the block (None: the
@@ -271,6 +281,32 @@ class BRWTDevice:
                                                               C.byref(h)), "mbrwt_create_from_columns_relaxed")
             else:
                 L.check(lib.mbrwt_create_from_columns(C.byref(d), device, C.byref(h)), "mbrwt_create_from_columns")
+        return cls(h)
+
+    @classmethod
+    def from_rows(cls, offsets, cols, num_columns, arity=8, shape=None, device=0):
+        """Row records straight from CSR rows (mbrwt_create_from_rows): row r
+        carries the columns cols[offsets[r]:offsets[r + 1]] (a set, any
+        order).  `shape` = dict with num_children, first_child, leaf_column
+        (BFS; e.g. the export of a tree built from a row sample), or None for
+        the basic partitioner's tree of `arity` (basic_shape).  No node image
+        and no dense column is built; the context's layout is 'rows'."""
+        lib = L.lib()
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if off.size == 0:
+            raise ValueError("offsets needs num_rows + 1 entries")
+        cl = np.ascontiguousarray(cols, dtype=np.uint32)
+        if cl.size == 0:
+            cl = np.zeros(1, dtype=np.uint32)
+        d = L.RowsDesc(off.size - 1, int(num_columns), _p(off, C.c_uint64), _p(cl, C.c_uint32))
+        sd = None
+        if shape is not None:
+            nc = np.ascontiguousarray(shape["num_children"], dtype=np.uint32)
+            fc = np.ascontiguousarray(shape["first_child"], dtype=np.uint32)
+            lc = np.ascontiguousarray(shape["leaf_column"], dtype=np.uint32)
+            sd = C.byref(L.ShapeDesc(len(nc), _p(nc, C.c_uint32), _p(fc, C.c_uint32), _p(lc, C.c_uint32)))
+        h = C.c_void_p()
+        L.check(lib.mbrwt_create_from_rows(C.byref(d), sd, int(arity), device, C.byref(h)), "mbrwt_create_from_rows")
         return cls(h)
 
     @classmethod

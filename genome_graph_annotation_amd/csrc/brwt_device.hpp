@@ -179,6 +179,23 @@ class BRWTDevice : public BinaryMatrix {
         return build_bottom_up(columns, num_rows, 2, device, relax_max_arity);
     }
 
+    // Row records straight from row-major data (mbrwt_create_from_rows): row r
+    // = cols[offsets[r] .. offsets[r+1]), a set in any order -- what the
+    // reference's annotators produce row by row (annotate_row, RowCompressed).
+    // shape == nullptr: the basic partitioner's tree of `arity`; else the
+    // given shape, e.g. that of a greedy + relaxed build of a row sample
+    static BRWTDevice build_from_rows(const std::vector<uint64_t> &offsets, const std::vector<uint32_t> &cols,
+                                      uint64_t num_columns, uint32_t arity = 8,
+                                      const mbrwt_shape_desc *shape = nullptr, int device = 0) {
+        if (offsets.empty()) throw std::invalid_argument("build_from_rows: offsets needs num_rows + 1 entries");
+        const mbrwt_rows_desc d{offsets.size() - 1, num_columns, offsets.data(), cols.data()};
+        BRWTDevice m(device);
+        mbrwt_ctx *c = nullptr;
+        check_status(mbrwt_create_from_rows(&d, shape, arity, device, &c), "mbrwt_create_from_rows");
+        m.ctx_.reset(c, Deleter());
+        return m;
+    }
+
     // a query handle over the same device image (mbrwt_ctx_clone): one per
     // server worker thread, so their get_rows calls do not serialise on a
     // shared workspace (the reference shares its annotator by reference

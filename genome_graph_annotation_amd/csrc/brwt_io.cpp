@@ -1035,6 +1035,28 @@ int mbrwt_tree_export(mbrwt_ctx *ctx, mbrwt_tree **out) {
     }
 }
 
+int mbrwt_tree_basic_shape(uint64_t num_columns, uint32_t arity, mbrwt_tree **out) {
+    if (!out) {
+        set_error("null output pointer");
+        return MBRWT_ERR_INVALID;
+    }
+    *out = nullptr;
+    try {
+        auto t = std::make_unique<mbrwt_tree>();
+        t->num_columns = num_columns;
+        const int rc = basic_shape(num_columns, arity, t->num_children, t->first_child, t->leaf_column);
+        if (rc) return rc;
+        t->vec_size.assign(t->num_children.size(), 0);
+        t->words.resize(t->num_children.size());
+        t->finish();
+        *out = t.release();
+        return MBRWT_OK;
+    } catch (const std::bad_alloc &) {
+        set_error("out of host memory");
+        return MBRWT_ERR_NOMEM;
+    }
+}
+
 const mbrwt_tree_desc *mbrwt_tree_get_desc(const mbrwt_tree *t) { return t ? &t->desc : nullptr; }
 
 int mbrwt_load(const uint8_t *bytes, uint64_t len, uint64_t *consumed, int device, mbrwt_ctx **out) {

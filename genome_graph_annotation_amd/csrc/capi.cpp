@@ -358,6 +358,65 @@ static int create_rows_ranged(int device, uint64_t num_rows, uint64_t num_column
         kNoLayoutHook);
 }
 
+// Row records straight from CSR rows under a tree shape (rows_from.hip;
+// DESIGN.md §11b): no node image at all, so the device holds the records
+// plus ONE range's labels.  Ranges are multiples of kRowsAlign rows; the
+// first (at most kRowsFirstRange rows) decides the record code and layout;
+// every range is cut from `offsets` so that its labels fit the memory left
+// (the 8 GiB reserve of create_rows_ranged) and the device sort's item count;
+// MBRWT_BUILD_ROWS_RANGE fixes the size.
+struct RowsFromEnd {
+    void operator()(RowsFrom *rf) const { rows_from_end(rf); }
+};
+static int create_from_rows(const mbrwt_rows_desc &desc, const Tree &shape, int device, mbrwt_ctx **out) {
+    const uint64_t n = desc.num_rows;
+    const uint64_t *off = desc.offsets;
+    return create_common(
+        device, out,
+        [&](Ctx &c) {
+            c.tree = shape;
+            c.tree.num_rows = n;
+            RowsFrom *rfp = nullptr;
+            if (int rc = rows_from_begin(c.tree, c.stream, &rfp)) return rc;
+            std::unique_ptr<RowsFrom, RowsFromEnd> rf(rfp);
+            // (auto_layout = false: there is no node image to fall back to)
+            RowsBuildPtr rb(rows_build_begin(c, n, kRowsAlign, false));
+            if (!rb) return (int)MBRWT_ERR_NOMEM;
+            const bool fixed = build_tuning().rows_range != 0;
+            // the largest range [a, a + k kRowsAlign), k kRowsAlign <= R, within the budget
+            auto cut = [&](uint64_t a, uint64_t R) {
+                uint64_t b = std::min(n, a + R);
+                if (fixed) return b;
+                size_t free_b = 0, total_b = 0;
+                (void)hipMemGetInfo(&free_b, &total_b);
+                const double left = (double)free_b - 8.0 * (1ull << 30) -
+                                    (double)rows_build_pending_bytes(rb.get(), n - a);
+                const double budget = std::max(left, (double)free_b / 8) / 1.2;
+                auto fits = [&](uint64_t e) {
+                    const uint64_t L = off[e] - off[a];
+                    return L <= kRowsFromMaxLabels && (double)rows_from_range_bytes(e - a, L) <= budget;
+                };
+                if (fits(b)) return b;
+                uint64_t lo = 1, hi = (b - a + kRowsAlign - 1) / kRowsAlign;  // lo: taken whatever it costs
+                while (lo + 1 < hi) {
+                    const uint64_t mid = (lo + hi) / 2;
+                    (fits(a + mid * kRowsAlign) ? lo : hi) = mid;
+                }
+                return std::min(n, a + lo * kRowsAlign);
+            };
+            for (uint64_t a = 0, b = 0; a < n; a = b) {
+                b = cut(a, fixed || a ? rows_range_rows() : std::min(rows_range_rows(), kRowsFirstRange));
+                if (int rc = rows_from_range(rf.get(), rb.get(), off, desc.cols, a, b, &c.tree.num_relations))
+                    return rc;  // (rb frees the build)
+            }
+            rf.reset();
+            if (int rc = rows_build_finish(rb.release())) return rc;
+            c.nodes_freed = true;
+            return (int)MBRWT_OK;
+        },
+        kNoLayoutHook);
+}
+
 // Layouts ROWS and AUTO over many rows build ranged: beyond kAutoRangedRows
 // the whole node image and the records side by side may not fit (C3: 214 GB
 // of node image + 160 GB of records).  AUTO falls back to the per-node
@@ -531,6 +590,59 @@ int mbrwt_create_from_columns(const mbrwt_columns_desc *desc, int device, mbrwt_
         return MBRWT_ERR_NOMEM;
     } catch (...) {
         set_error("unexpected exception in mbrwt_create_from_columns");
+        return MBRWT_ERR_INVALID;
+    }
+}
+
+int mbrwt_create_from_rows(const mbrwt_rows_desc *desc, const mbrwt_shape_desc *shape, uint32_t arity, int device,
+                           mbrwt_ctx **out) {
+    if (!desc || !out) {
+        set_error("null rows description or output pointer");
+        return MBRWT_ERR_INVALID;
+    }
+    *out = nullptr;
+    try {
+        const int layout = resolve_layout();
+        if (layout == LAYOUT_NODES || layout == LAYOUT_BOTH) {
+            set_error("mbrwt_create_from_rows builds row records only: layout AUTO or ROWS");
+            return MBRWT_ERR_UNSUPPORTED;
+        }
+        const uint64_t n = desc->num_rows, m = desc->num_columns;
+        if (n == 0 || m == 0) {  // the context of the same empty matrix from its (empty) columns
+            std::vector<const uint64_t *> none(m, nullptr);
+            const mbrwt_columns_desc cd{n, m, none.data(), shape ? 2u : arity};
+            return mbrwt_create_from_columns(&cd, device, out);
+        }
+        if (!desc->offsets || desc->offsets[0] != 0 || (desc->offsets[n] && !desc->cols)) {
+            set_error("row offsets: null array or first offset not 0");
+            return MBRWT_ERR_INVALID;
+        }
+        for (uint64_t r = 0; r < n; ++r) {
+            if (desc->offsets[r + 1] < desc->offsets[r]) {
+                set_error("row offsets not ascending");
+                return MBRWT_ERR_INVALID;
+            }
+            // (rows are sets: more labels than columns repeat one)
+            if (desc->offsets[r + 1] - desc->offsets[r] > m) {
+                set_error("a row of more labels than columns");
+                return MBRWT_ERR_INVALID;
+            }
+        }
+        Tree tree;
+        if (shape) {
+            if (const int rc = shape_tree(*shape, m, tree)) return rc;
+        } else {
+            std::vector<uint32_t> nc, fc, lc;
+            if (const int rc = basic_shape(m, arity, nc, fc, lc)) return rc;
+            const mbrwt_shape_desc sd{(uint32_t)nc.size(), nc.data(), fc.data(), lc.data()};
+            if (const int rc = shape_tree(sd, m, tree)) return rc;
+        }
+        return create_from_rows(*desc, tree, device, out);
+    } catch (const std::bad_alloc &) {
+        set_error("host allocation failed");
+        return MBRWT_ERR_NOMEM;
+    } catch (...) {
+        set_error("unexpected exception in mbrwt_create_from_rows");
         return MBRWT_ERR_INVALID;
     }
 }

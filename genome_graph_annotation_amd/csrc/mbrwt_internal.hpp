@@ -364,6 +364,24 @@ inline void destroy_fence(WsFenceState &st) {
     st.live = false;
 }
 
+// ROW SOURCES of the row-record build (rows_emit.hpp): what a builder reads a
+// row's masks from -- a node image (Ctx::d_nodes), or the row's LABELS over a
+// tree shape (mbrwt_create_from_rows, rows_from.hip): per
+// dnode its children and the half-open interval [lo, hi) of pre-order leaf
+// indices below it, and per row its keys (pre-order leaf indices) ascending.
+struct LabelNode {
+    uint32_t first_child;  // dnode of child 0 (internal nodes)
+    uint32_t arity;        // children; kShapeLeaf for a leaf
+    uint32_t lo, hi;       // pre-order leaf indices below the node
+};
+static_assert(sizeof(LabelNode) == 16, "LabelNode must be 16 bytes");
+constexpr uint32_t kShapeLeaf = 0x80000000u;
+struct LabelRows {
+    const LabelNode *shape = nullptr;  // null: the rows come from a node image
+    const uint32_t *off = nullptr;     // rows + 1 offsets into keys (of the range)
+    const uint16_t *keys = nullptr;
+};
+
 struct HostPipe;  // hostpipe.cpp: the chunked host-buffer get_rows
 void free_host_pipe(HostPipe *p);
 
@@ -428,6 +446,9 @@ struct Ctx {
     // `nodes_freed` = the per-node images were dropped after the records were
     // built (layout ROWS), so only the row-record kernels can answer
     RowsImage rows;
+    // a range of a build from rows (rows_from.hip): its rows' labels, the
+    // record builders' source instead of d_nodes (tree: the shape alone)
+    LabelRows label_rows;
     bool nodes_freed = false;
     bool rows_sc_dirty = true;   // the row-record kernels' counters (in ws_counts) need clearing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> async_ev;  // timing of asynchronous calls
@@ -461,6 +482,28 @@ struct RowsBuildAbort {
 };
 using RowsBuildPtr = std::unique_ptr<RowsBuild, RowsBuildAbort>;
 void free_rows(RowsImage &r);
+// the message of a tree outside the row-record limits (prepare_tables)
+const char *rows_limits_message();
+// shapes without data (rows_shape.cpp): the basic partitioner's tree as BFS
+// arrays; the Tree of a shape (dnode table, pre-order labels, no image)
+int basic_shape(uint64_t m, uint32_t arity, std::vector<uint32_t> &num_children, std::vector<uint32_t> &first_child,
+                std::vector<uint32_t> &leaf_column);
+int shape_tree(const mbrwt_shape_desc &shape, uint64_t num_columns, Tree &tree);
+// row records straight from CSR rows (rows_from.hip): the shape's device
+// table and the column -> pre-order index map once (rows_from_begin), then
+// per range [a, b) of rows the upload, the keys, the order check (a sort only
+// where a row is not ascending) and rows_build_range with the label source at
+// row a; *labels += the range's labels.  The device holds the records plus
+// ONE range's labels.
+struct RowsFrom;
+int rows_from_begin(const Tree &shape, hipStream_t s, RowsFrom **out);
+int rows_from_range(RowsFrom *rf, RowsBuild *rb, const uint64_t *offsets, const uint32_t *cols, uint64_t a, uint64_t b,
+                    uint64_t *labels);
+void rows_from_end(RowsFrom *rf);
+// device bytes one range of `rows` rows and `labels` labels takes beside the
+// records (the sizing of the ranges, capi.cpp), and the most labels of a range
+uint64_t rows_from_range_bytes(uint64_t rows, uint64_t labels);
+constexpr uint64_t kRowsFromMaxLabels = 0x7FFFFFFFull;  // (the device sort counts its items in an int)
 // launch grid of a grid-stride kernel over `items`: workgroups of 256
 // threads, one thread per item up to 65536 workgroups
 inline unsigned grid256(uint64_t items) {

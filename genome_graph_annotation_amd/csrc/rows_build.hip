@@ -12,6 +12,11 @@
 // allocates the image; the rules and the cost model are pure host code in
 // rows_plan.hpp.  write_range: one thread per block writes the block and its
 // spill entries (k_rows_write).  RowsBuild's destructor is the one release.
+//
+// The kernels are generic over the rows' SOURCE (rows_emit.hpp): the node
+// image of the range, or -- a range of mbrwt_create_from_rows, whose Ctx
+// carries label_rows and the shape as its tree (rows_from.hip) -- the rows'
+// labels walked over the shape; every step of the driver is the same.
 #include <algorithm>
 #include <memory>
 #include <optional>
@@ -47,12 +52,11 @@ namespace {
 // (build_term_tables).  False when the row has more than kTermMaxMasks masks
 // or its masks do not follow the table.
 constexpr uint32_t kTermMaxMasks = 256;
-template <class Term>
-__device__ bool row_terms(const DevNode *nodes, bool folded, uint32_t r, const uint32_t *bt, Term term,
-                          uint32_t &labels) {
+template <class Src, class Term>
+__device__ bool row_terms(const Src &src, uint32_t r, const uint32_t *bt, Term term, uint32_t &labels) {
     uint16_t mb[kTermMaxMasks];
     uint32_t nm = 0;
-    labels = emit_row_masks(nodes, folded, r, [&](uint64_t mk, uint32_t, uint32_t) {
+    labels = src.masks(r, [&](uint64_t mk, uint32_t, uint32_t) {
         if (nm < kTermMaxMasks) mb[nm] = (uint16_t)mk;
         ++nm;
     });
@@ -101,12 +105,13 @@ __device__ bool row_terms(const DevNode *nodes, bool folded, uint32_t r, const u
 }
 // row r's terminal fields (w bits: id | mask << ib) from byte p on; the
 // bytes written, or ~0u
-__device__ __forceinline__ uint32_t write_row_terms(const DevNode *nodes, bool folded, uint32_t r, uint8_t *p,
-                                                    const uint32_t *bt, uint32_t w, uint32_t ib, uint32_t &labels) {
+template <class Src>
+__device__ __forceinline__ uint32_t write_row_terms(const Src &src, uint32_t r, uint8_t *p, const uint32_t *bt,
+                                                    uint32_t w, uint32_t ib, uint32_t &labels) {
     uint64_t acc = 0;
     uint32_t nb = 0, wr = 0;
     const bool ok = row_terms(
-        nodes, folded, r, bt,
+        src, r, bt,
         [&](uint32_t id, uint32_t m) {
             acc |= (uint64_t)(id | (m << ib)) << nb;
             nb += w;
@@ -124,15 +129,16 @@ __device__ __forceinline__ uint32_t write_row_terms(const DevNode *nodes, bool f
 // per row of a range: record size (1 + mask bytes, < 2^15) | 0x8000 when the
 // row has >= 255 labels (its count does not fit the inline byte)
 // (nib: the masks as nibble codes, rows_record.hpp RecMasks)
-__global__ __launch_bounds__(256) void k_rows_measure(const DevNode *nodes, uint32_t folded, uint64_t n, uint16_t *sz,
-                                                      unsigned long long *acc, uint32_t code, const uint32_t *bt,
-                                                      uint32_t w) {
+// (Src: the rows' source, rows_emit.hpp -- a node image or the rows' labels)
+template <class Src>
+__global__ __launch_bounds__(256) void k_rows_measure(Src src, uint64_t n, uint16_t *sz, unsigned long long *acc,
+                                                      uint32_t code, const uint32_t *bt, uint32_t w) {
     const bool nib = code == 1u;
     unsigned long long lab = 0, bytes = 0, bad = 0, bytes1 = 0;
     const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gs) {
         uint32_t b = 1, nn = 0, b1 = 1;
-        uint32_t L = emit_row_masks(nodes, folded != 0, (uint32_t)r, [&](uint64_t mk, uint32_t a, uint32_t) {
+        uint32_t L = src.masks((uint32_t)r, [&](uint64_t mk, uint32_t a, uint32_t) {
             if (nib) nn += nib_codes((uint32_t)mk);
             else b += rec_mask_bytes(a);
             b1 += rec_mask_bytes(a);
@@ -140,7 +146,7 @@ __global__ __launch_bounds__(256) void k_rows_measure(const DevNode *nodes, uint
         b += (nn + 1) / 2;
         if (code == 2u && L != ~0u) {  // terminal records: the fields' bytes
             uint32_t nt = 0, L2 = 0;
-            b = row_terms(nodes, folded != 0, (uint32_t)r, bt, [&](uint32_t, uint32_t) { ++nt; }, L2) && L2 == L
+            b = row_terms(src, (uint32_t)r, bt, [&](uint32_t, uint32_t) { ++nt; }, L2) && L2 == L
                     ? 1u + (nt * w + 7u) / 8u
                     : 0x8000u;  // (a row the fields cannot hold: bad)
         }
@@ -230,15 +236,16 @@ __global__ __launch_bounds__(256) void k_rows_plan(const uint16_t *sz, uint64_t 
 
 // the masks of row r written from byte p on (bytes, or nibble codes); the
 // bytes written
-__device__ __forceinline__ uint32_t write_row_masks(const DevNode *nodes, bool folded, uint32_t r, uint8_t *p,
-                                                    uint32_t nib, uint32_t &labels) {
+template <class Src>
+__device__ __forceinline__ uint32_t write_row_masks(const Src &src, uint32_t r, uint8_t *p, uint32_t nib,
+                                                    uint32_t &labels) {
     uint32_t w = 0;
     auto put = [&](uint32_t v) {  // nibble w: byte w / 2, low half first
         if (w & 1u) p[w >> 1] |= (uint8_t)(v << 4);
         else p[w >> 1] = (uint8_t)v;
         ++w;
     };
-    labels = emit_row_masks(nodes, folded, r, [&](uint64_t mk, uint32_t a, uint32_t) {
+    labels = src.masks(r, [&](uint64_t mk, uint32_t a, uint32_t) {
         if (nib) {  // (arity <= 8)
             if (nib_codes((uint32_t)mk) == 1u) {
                 put((uint32_t)__builtin_ctzll(mk));
@@ -255,14 +262,14 @@ __device__ __forceinline__ uint32_t write_row_masks(const DevNode *nodes, bool f
 }
 
 // one thread per block of the range: header, inline records, spill entries
-__global__ __launch_bounds__(256) void k_rows_write(const DevNode *nodes, uint32_t folded, uint64_t nr_range,
-                                                    const uint16_t *sz, uint32_t B, uint32_t S, uint8_t *blocks,
-                                                    uint8_t *spill, unsigned long long *spill_used, uint32_t code,
-                                                    const uint32_t *bt, uint32_t w, uint32_t ib) {
+template <class Src>
+__global__ __launch_bounds__(256) void k_rows_write(Src src, uint64_t nr_range, const uint16_t *sz, uint32_t B,
+                                                    uint32_t S, uint8_t *blocks, uint8_t *spill,
+                                                    unsigned long long *spill_used, uint32_t code, const uint32_t *bt,
+                                                    uint32_t w, uint32_t ib) {
     const uint32_t nib = code == 1u ? 1u : 0u;
     auto write = [&](uint32_t r, uint8_t *p, uint32_t &L) -> uint32_t {
-        return code == 2u ? write_row_terms(nodes, folded != 0, r, p, bt, w, ib, L)
-                          : write_row_masks(nodes, folded != 0, r, p, nib, L);
+        return code == 2u ? write_row_terms(src, r, p, bt, w, ib, L) : write_row_masks(src, r, p, nib, L);
     };
     const uint64_t nb = (nr_range + S - 1) / S;
     const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
@@ -375,6 +382,11 @@ RowsBuild::~RowsBuild() {
 
 void rows_build_abort(RowsBuild *rb) { delete rb; }
 
+const char *rows_limits_message() {
+    return "tree shape outside the row-record limits (arity <= 64, columns < 2^16, height <= 16, a walk table of <= "
+           "8192 words)";
+}
+
 static int read_acc(RowsBuild &rb, unsigned long long *h, int k) {
     MBRWT_HIP(hipMemcpyAsync(h, rb.d_acc, k * sizeof(unsigned long long), hipMemcpyDeviceToHost, rb.s));
     MBRWT_HIP(hipStreamSynchronize(rb.s));
@@ -416,7 +428,7 @@ static int prepare_tables(RowsBuild &rb, Ctx &range) {
     if (!build_rwt_table(range.tree, im.table, im.height, im.max_arity) ||
         !build_rwt2_table(range.tree, im.table2, im.frames, &im.slot_dnode)) {
         im.table.clear();
-        set_error("tree shape outside the row-record limits (arity <= 64, columns < 2^16, height <= 16, a walk table of <= 8192 words)");
+        set_error(rows_limits_message());
         return MBRWT_ERR_UNSUPPORTED;
     }
     // one-byte masks everywhere (rows_walk6): the root and every internal
@@ -477,9 +489,10 @@ static int measure_range(RowsBuild &rb, Ctx &range, Measure &h) {
     const RowsImage &im = rb.img;
     const uint64_t nr = range.tree.num_rows;
     MBRWT_HIP(hipMemsetAsync(rb.d_acc, 0, 8 * sizeof(unsigned long long), rb.s));
-    hipLaunchKernelGGL(k_rows_measure, dim3(grid256(nr)), dim3(256), 0, rb.s, range.d_nodes,
-                       range.tree.folded ? 1u : 0u, nr, rb.d_sz, rb.d_acc, record_code(im), (const uint32_t *)rb.d_bt,
-                       term_width(im));
+    with_row_source(range, [&](auto src) {
+        hipLaunchKernelGGL(k_rows_measure<decltype(src)>, dim3(grid256(nr)), dim3(256), 0, rb.s, src, nr, rb.d_sz,
+                           rb.d_acc, record_code(im), (const uint32_t *)rb.d_bt, term_width(im));
+    });
     MBRWT_HIP(hipGetLastError());
     unsigned long long a[4];
     if (int rc = read_acc(rb, a, 4)) return rc;
@@ -630,10 +643,11 @@ static int write_range(RowsBuild &rb, Ctx &range, uint64_t row0) {
     im.spilled_rows += pc.spilled;
     im.long_rows += pc.long_rows;
     im.spill_bytes += pc.units * 16;
-    hipLaunchKernelGGL(k_rows_write, dim3(grid256((nr + im.S - 1) / im.S)), dim3(256), 0, rb.s, range.d_nodes,
-                       range.tree.folded ? 1u : 0u, nr, rb.d_sz, im.B, im.S, im.blocks + (row0 / im.S) * im.B,
-                       im.spill, im.d_spill_used, record_code(im), (const uint32_t *)rb.d_bt, term_width(im),
-                       term_id_bits(im));
+    with_row_source(range, [&](auto src) {
+        hipLaunchKernelGGL(k_rows_write<decltype(src)>, dim3(grid256((nr + im.S - 1) / im.S)), dim3(256), 0, rb.s, src,
+                           nr, rb.d_sz, im.B, im.S, im.blocks + (row0 / im.S) * im.B, im.spill, im.d_spill_used,
+                           record_code(im), (const uint32_t *)rb.d_bt, term_width(im), term_id_bits(im));
+    });
     MBRWT_HIP(hipGetLastError());
     MBRWT_HIP(hipStreamSynchronize(rb.s));
     return MBRWT_OK;
@@ -647,7 +661,8 @@ int rows_build_range(RowsBuild *rbp, Ctx &range, uint64_t row0) {
     RowsImage &im = rb.img;
     const uint64_t nr = range.tree.num_rows;
     if (!nr) return MBRWT_OK;
-    if (!range.d_nodes || range.tree.nodes.empty()) {
+    // (a range of a build from rows brings its labels instead, rows_from.hip)
+    if ((!range.d_nodes && !range.label_rows.shape) || range.tree.nodes.empty()) {
         set_error("row records need a node image");
         return MBRWT_ERR_UNSUPPORTED;
     }

@@ -1,6 +1,7 @@
-// rows_emit.hpp -- the masks of a row's descent over a node image (any of
-// its kinds), in DFS pre-order: what the row-record builders (rows_build.hip,
-// rows_var.hip) store per row.  Device code shared by both translation units.
+// rows_emit.hpp -- the masks of a row's descent in DFS pre-order: what the
+// row-record builders (rows_build.hip, rows_var.hip) store per row, read from
+// a node image (any of its kinds) or from the row's labels over a tree shape
+// (the row SOURCES at the end).  Device code shared by both translation units.
 #pragma once
 
 #include "device_access.hpp"
@@ -185,6 +186,100 @@ __device__ uint32_t emit_row_masks(const DevNode *__restrict__ nodes, bool folde
         visit(w, rb.x + (uint32_t)__builtin_popcount(rb.y & ((1u << (j & 31)) - 1u)));
     }
     return bad ? ~0u : leaves;
+}
+
+// ------------------------------------------------------------------------
+// build: the masks of a row's descent from the row's labels
+// ------------------------------------------------------------------------
+constexpr int kLabelFrames = (int)kRowsMaxHeight + 1;  // internal levels on a path + one
+
+// Row r of a label source: the same emit calls and return value as
+// emit_row_masks, from the row's keys (pre-order leaf indices, ascending,
+// no duplicate) walked over the shape table.  The keys below a node are one
+// run of the row's keys and its children's intervals follow each other, so
+// at node v bit c of the mask is set iff a key of v's run lies in child c's
+// interval: one pass over the run gives the mask (emitted before the
+// children, pre-order), then every set internal child takes its part of the
+// run in child order.  One lane, a stack of kLabelFrames frames; the emitted
+// dnodes are the shape's (super-root 0, root 1).
+template <class Emit>
+__device__ uint32_t emit_label_masks(const LabelRows &src, uint32_t r, Emit emit) {
+    const uint32_t a0 = gld(src.off + r), b0 = gld(src.off + r + 1);
+    if (a0 == b0) return 0;
+    const LabelNode root = gld(src.shape + 1);
+    if (root.arity & kShapeLeaf) return 1;
+    uint32_t ffc[kLabelFrames], fp[kLabelFrames], fe[kLabelFrames];
+    uint64_t fm[kLabelFrames];
+    int sp = 0;
+    uint32_t leaves = 0;
+    bool bad = false;
+    // internal dnode v over the keys [p, e): its mask, then a frame
+    auto visit = [&](uint32_t v, const LabelNode &nd, uint32_t p, uint32_t e) {
+        uint64_t m = 0;
+        uint32_t c = 0, hi = gld(src.shape + nd.first_child).hi;
+        for (uint32_t q = p; q < e; ++q) {
+            const uint32_t k = gld(src.keys + q);
+            while (k >= hi && c + 1 < nd.arity) hi = gld(src.shape + nd.first_child + ++c).hi;
+            m |= 1ull << c;
+        }
+        emit(m, nd.arity, v);
+        if (sp == kLabelFrames) {
+            bad = true;
+            return;
+        }
+        ffc[sp] = nd.first_child;
+        fm[sp] = m;
+        fp[sp] = p;
+        fe[sp] = e;
+        ++sp;
+    };
+    visit(1u, root, a0, b0);
+    while (sp > 0 && !bad) {
+        const int t = sp - 1;
+        if (!fm[t]) {
+            --sp;
+            continue;
+        }
+        const uint32_t c = (uint32_t)__builtin_ctzll(fm[t]);
+        fm[t] &= fm[t] - 1;
+        const uint32_t w = ffc[t] + c;
+        const LabelNode nw = gld(src.shape + w);
+        uint32_t q = fp[t];
+        const uint32_t e = fe[t];
+        while (q < e && gld(src.keys + q) < nw.hi) ++q;  // the child's keys: [fp, q)
+        const uint32_t p = fp[t];
+        fp[t] = q;
+        if (nw.arity & kShapeLeaf) {
+            ++leaves;
+            continue;
+        }
+        visit(w, nw, p, q);
+    }
+    return bad ? ~0u : leaves;
+}
+
+// The row sources of the record builders (rows_build.hip, rows_var.hip):
+// masks(r, emit) as emit_row_masks
+struct NodeSource {
+    const DevNode *nodes;
+    uint32_t folded;
+    template <class Emit>
+    __device__ __forceinline__ uint32_t masks(uint32_t r, Emit emit) const {
+        return emit_row_masks(nodes, folded != 0, r, emit);
+    }
+};
+struct LabelSource {
+    LabelRows rows;
+    template <class Emit>
+    __device__ __forceinline__ uint32_t masks(uint32_t r, Emit emit) const {
+        return emit_label_masks(rows, r, emit);
+    }
+};
+// fn(source) on the source of a build range: its labels, else its node image
+template <class Fn>
+inline void with_row_source(const Ctx &range, Fn fn) {
+    if (range.label_rows.shape) fn(LabelSource{range.label_rows});
+    else fn(NodeSource{range.d_nodes, range.tree.folded ? 1u : 0u});
 }
 
 }  // namespace

@@ -108,14 +108,16 @@ constexpr uint32_t kLineRows = 13;
 constexpr uint32_t kOffBits = 17;  // 4-byte units from the line's base
 
 // per row of a range: record length in 4-byte units and label count
-__global__ __launch_bounds__(256) void k_var_measure(const DevNode *nodes, uint32_t folded, uint64_t n,
-                                                     const uint16_t *__restrict__ unit_of, uint32_t W, uint16_t *units,
-                                                     uint16_t *cnt, unsigned long long *acc) {
+// (Src: the rows' source, rows_emit.hpp)
+template <class Src>
+__global__ __launch_bounds__(256) void k_var_measure(Src src, uint64_t n, const uint16_t *__restrict__ unit_of,
+                                                     uint32_t W, uint16_t *units, uint16_t *cnt,
+                                                     unsigned long long *acc) {
     unsigned long long lab = 0, bytes = 0, bad = 0;
     const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gs) {
         uint32_t items = 0, labels = 0;
-        const uint32_t L = emit_row_masks(nodes, folded != 0, (uint32_t)r, [&](uint32_t m, uint32_t, uint32_t d) {
+        const uint32_t L = src.masks((uint32_t)r, [&](uint32_t m, uint32_t, uint32_t d) {
             if (gld(unit_of + d) != 0xFFFFu) {
                 ++items;
                 labels += (uint32_t)__builtin_popcount(m);
@@ -146,9 +148,9 @@ __global__ __launch_bounds__(256) void k_var_measure(const DevNode *nodes, uint3
 }
 
 // per row of a range: its record at chunk + 4 off[r] (the chunk is zeroed)
-__global__ __launch_bounds__(256) void k_var_write(const DevNode *nodes, uint32_t folded, uint64_t n,
-                                                   const uint16_t *__restrict__ unit_of, uint32_t W,
-                                                   const uint64_t *__restrict__ off, uint8_t *chunk) {
+template <class Src>
+__global__ __launch_bounds__(256) void k_var_write(Src src, uint64_t n, const uint16_t *__restrict__ unit_of,
+                                                   uint32_t W, const uint64_t *__restrict__ off, uint8_t *chunk) {
     const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gs) {
         const uint64_t o = gld(off + r);
@@ -156,7 +158,7 @@ __global__ __launch_bounds__(256) void k_var_write(const DevNode *nodes, uint32_
         uint32_t *rec = reinterpret_cast<uint32_t *>(chunk + 4 * o);
         uint32_t cw = 0, cv = 0;  // the bitmap word being filled
         uint32_t mi = 0, mv = 0;  // mask bytes so far, the word being filled
-        (void)emit_row_masks(nodes, folded != 0, (uint32_t)r, [&](uint32_t m, uint32_t, uint32_t d) {
+        (void)src.masks((uint32_t)r, [&](uint32_t m, uint32_t, uint32_t d) {
             const uint32_t u = gld(unit_of + d);
             if (u == 0xFFFFu) return;
             if ((u >> 5) != cw) {
@@ -222,8 +224,10 @@ int var_build_range(RowsImage &im, const Ctx &range, uint64_t row0, VarScratch &
     }
     MBRWT_HIP(hipMemsetAsync(d_acc, 0, 64, s));
     MBRWT_HIP(hipMemsetAsync(d_units + nr, 0, 2, s));
-    hipLaunchKernelGGL(k_var_measure, dim3(grid256(nr)), dim3(256), 0, s, range.d_nodes, range.tree.folded ? 1u : 0u,
-                       nr, im.d_unit_of, im.var_W, d_units, d_cnt, d_acc);
+    with_row_source(range, [&](auto src) {
+        hipLaunchKernelGGL(k_var_measure<decltype(src)>, dim3(grid256(nr)), dim3(256), 0, s, src, nr, im.d_unit_of,
+                           im.var_W, d_units, d_cnt, d_acc);
+    });
     MBRWT_HIP(hipGetLastError());
     hipcub::TransformInputIterator<uint64_t, Widen<uint16_t>, const uint16_t *> it(d_units, Widen<uint16_t>());
     size_t sb = 0;
@@ -252,8 +256,10 @@ int var_build_range(RowsImage &im, const Ctx &range, uint64_t row0, VarScratch &
     im.var_rec_bytes += 4 * units;
     im.record_bytes += 4 * units;
     MBRWT_HIP(hipMemsetAsync(chunk, 0, bytes, s));
-    hipLaunchKernelGGL(k_var_write, dim3(grid256(nr)), dim3(256), 0, s, range.d_nodes, range.tree.folded ? 1u : 0u,
-                       nr, im.d_unit_of, im.var_W, d_off, reinterpret_cast<uint8_t *>(chunk));
+    with_row_source(range, [&](auto src) {
+        hipLaunchKernelGGL(k_var_write<decltype(src)>, dim3(grid256(nr)), dim3(256), 0, s, src, nr, im.d_unit_of,
+                           im.var_W, d_off, reinterpret_cast<uint8_t *>(chunk));
+    });
     MBRWT_HIP(hipGetLastError());
     MBRWT_HIP(hipMemsetAsync(d_acc, 0, 64, s));
     hipLaunchKernelGGL(k_var_lines, dim3(grid256((nr + kLineRows - 1) / kLineRows)), dim3(256), 0, s, d_off, d_cnt,
@@ -280,9 +286,11 @@ int var_measure_range(RowsImage &im, const Ctx &range, VarScratch &ws, uint64_t 
     }
     unsigned long long *d_acc = reinterpret_cast<unsigned long long *>(ws.acc.buf);
     MBRWT_HIP(hipMemsetAsync(d_acc, 0, 64, s));
-    hipLaunchKernelGGL(k_var_measure, dim3(grid256(nr)), dim3(256), 0, s, range.d_nodes, range.tree.folded ? 1u : 0u,
-                       nr, im.d_unit_of, im.var_W, reinterpret_cast<uint16_t *>(ws.units.buf),
-                       reinterpret_cast<uint16_t *>(ws.cnt.buf), d_acc);
+    with_row_source(range, [&](auto src) {
+        hipLaunchKernelGGL(k_var_measure<decltype(src)>, dim3(grid256(nr)), dim3(256), 0, s, src, nr, im.d_unit_of,
+                           im.var_W, reinterpret_cast<uint16_t *>(ws.units.buf),
+                           reinterpret_cast<uint16_t *>(ws.cnt.buf), d_acc);
+    });
     MBRWT_HIP(hipGetLastError());
     unsigned long long h[3];
     MBRWT_HIP(hipMemcpyAsync(h, d_acc, sizeof(h), hipMemcpyDeviceToHost, s));

@@ -149,6 +149,58 @@ int mbrwt_create_from_columns_relaxed(const mbrwt_columns_desc *desc, uint64_t r
                                       mbrwt_ctx **out);
 int mbrwt_create_relaxed(const mbrwt_tree_desc *desc, uint64_t max_arity, int device, mbrwt_ctx **out);
 
+/*
+ * Build the row records straight from row-major data: the
+ * rows as a CSR (as mbrwt_binrel_desc, mbrwt_wt.h) plus a tree SHAPE.  A row's
+ * record is a function of its label set and the shape alone, and the BRWT
+ * over a given shape is unique, so the context answers every query -- and
+ * mbrwt_tree_export gives every index column -- exactly as the ROWS context
+ * mbrwt_create builds from that tree; but no node image and no dense column
+ * ever exists: the device holds the records plus one range's labels (ranges
+ * of multiples of 360,360 rows; the first, at most 64 x 360,360 rows, decides
+ * the record code and layout; later ones are sized from the free device
+ * memory less an 8 GiB reserve, at most 2^31 - 1 labels each;
+ * MBRWT_BUILD_ROWS_RANGE fixes the size).  This is how a matrix too large for
+ * mbrwt_create_from_columns (num_columns x ceil(num_rows / 64) words on the
+ * host and the device) is built from data: the shape from a build of a row
+ * sample (as binary_grouping_greedy samples 10^6 rows,
+ * partitionings.cpp:148-196), the records from all rows, a .brwt through
+ * mbrwt_tree_export + mbrwt_tree_serialize.  The reference's annotators
+ * produce such rows (annotate_row, RowCompressed).
+ *
+ * shape == NULL: the basic partitioner's tree of `arity` (2..64) over
+ * num_columns (mbrwt_tree_basic_shape); else the given shape (arity ignored):
+ * BFS arrays as documented for mbrwt_shape_desc, node arity up to 64, whose
+ * leaves' leaf_column must be a permutation of 0..num_columns-1
+ * (MBRWT_ERR_INVALID otherwise, also when the leaf count differs).
+ * Layout: always MBRWT_LAYOUT_ROWS.  The thread's MBRWT_BUILD_LAYOUT must be
+ * AUTO or ROWS (NODES, BOTH: MBRWT_ERR_UNSUPPORTED -- there is no node image
+ * to build); AUTO's decline of records above 1.25 requests per row does not
+ * apply (there is nothing to fall back to).  Every other record option of the
+ * calling thread is honoured as in a ROWS build from a tree
+ * (MBRWT_BUILD_ROWS_CODE, _BLOCK, _VAR, _VAR_LANES, _CLASSES, _FOOTPRINT,
+ * _RANGE, _ROWS_WGS_PER_CU).  A tree outside the row-record limits (a
+ * one-column tree, arity > 64, columns beyond the records' u16 labels,
+ * height > 16, a walk table over 8,192 words, a row of more than 32,767
+ * labels in any range) ->
+ * MBRWT_ERR_UNSUPPORTED with the messages of layout ROWS.
+ * Rows are sets, their columns in any order: a column id >= num_columns or a
+ * column listed twice in a row -> MBRWT_ERR_INVALID (both checked on the
+ * device, as mbrwt_wt_create); offsets[0] != 0, descending offsets or null
+ * arrays -> MBRWT_ERR_INVALID, checked on the host before any device call.
+ * A null desc or out -> MBRWT_ERR_INVALID, with or without a GPU.
+ * num_rows == 0 or num_columns == 0: the context mbrwt_create_from_columns
+ * gives for the same empty matrix.  mbrwt_num_relations = the total number of
+ * labels; mbrwt_num_nodes comes from the shape.
+ */
+typedef struct mbrwt_rows_desc {
+    uint64_t num_rows, num_columns;
+    const uint64_t *offsets; /* num_rows + 1, offsets[0] = 0, ascending */
+    const uint32_t *cols;    /* row r: cols[offsets[r] .. offsets[r+1]), any order */
+} mbrwt_rows_desc;
+int mbrwt_create_from_rows(const mbrwt_rows_desc *desc, const mbrwt_shape_desc *shape, uint32_t arity, int device,
+                           mbrwt_ctx **out);
+
 void mbrwt_destroy(mbrwt_ctx *ctx);
 
 /* A second query context over the SAME device image (no copy): its own
@@ -373,6 +425,13 @@ typedef struct mbrwt_tree mbrwt_tree;
 int mbrwt_tree_parse(const uint8_t *bytes, uint64_t len, uint64_t *consumed, mbrwt_tree **out);
 int mbrwt_tree_serialize(const mbrwt_tree_desc *desc, uint8_t *buf, uint64_t cap, uint64_t *needed);
 int mbrwt_tree_export(mbrwt_ctx *ctx, mbrwt_tree **out);
+/* The shape BRWTBottomUpBuilder::build gives with get_basic_partitioner(arity)
+   (BRWT_builders.cpp:20-31, :119-163; groups of one pass through, so leaves
+   may sit at mixed depths): an owned mbrwt_tree with every vec_size 0 (and
+   num_rows 0) -- the shape mbrwt_create_from_rows takes for shape == NULL.
+   arity outside 2..64 -> MBRWT_ERR_INVALID; num_columns == 0 gives the empty
+   tree.  Host only, no GPU. */
+int mbrwt_tree_basic_shape(uint64_t num_columns, uint32_t arity, mbrwt_tree **out);
 const mbrwt_tree_desc *mbrwt_tree_get_desc(const mbrwt_tree *tree); /* valid until mbrwt_tree_free */
 void mbrwt_tree_free(mbrwt_tree *tree);
 int mbrwt_load(const uint8_t *bytes, uint64_t len, uint64_t *consumed, int device, mbrwt_ctx **out);

@@ -26,6 +26,8 @@ ap.add_argument("--density", type=float, default=0.003)
 ap.add_argument("--arity", type=int, default=8)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--relax", type=int, default=0, help="then BRWTOptimizer::relax with this max arity")
+ap.add_argument("--from-rows", action="store_true",
+                help="the same matrix through from_rows (CSR rows) and from_columns(layout='rows'), reps alternating")
 a = ap.parse_args()
 
 import oracle as O  # checker + CPU baseline only
@@ -35,6 +37,83 @@ n, m = a.rows, a.cols
 W = (n + 63) // 64
 words = O.generate_columns(n, m, a.density, seed=42)
 cols = words[: m * W].reshape(m, W)
+
+
+
+def csr_rows(cols, n):
+    """The matrix's rows as a CSR (ascending columns per row), from its column words."""
+    off = np.zeros(n + 1, dtype=np.uint64)
+    parts = []
+    for r0 in range(0, n, 1 << 16):
+        r1 = min(n, r0 + (1 << 16))
+        bits = np.unpackbits(cols[:, r0 // 64:(r1 + 63) // 64].view(np.uint8), axis=1, bitorder="little")
+        rr, cc = np.nonzero(bits[:, : r1 - r0].T)
+        off[r0 + 1:r1 + 1] = np.bincount(rr, minlength=r1 - r0)
+        parts.append(cc.astype(np.uint32))
+    return np.cumsum(off, dtype=np.uint64), np.concatenate(parts)
+
+
+class LowWater:
+    """The low-water mark of hipMemGetInfo's free bytes while the block runs
+    (sampled around it and by a thread during it)."""
+
+    def __enter__(self):
+        import threading
+        import torch
+        self._info = lambda: torch.cuda.mem_get_info()[0]
+        self.before = self.low = self._info()
+        self._stop = threading.Event()
+
+        def poll():
+            while not self._stop.is_set():
+                self.low = min(self.low, self._info())
+                time.sleep(0.0005)
+        self._t = threading.Thread(target=poll, daemon=True)
+        self._t.start()
+        return self
+
+    def __exit__(self, *exc):
+        self._stop.set()
+        self._t.join()
+        self.low = min(self.low, self._info())
+
+
+if a.from_rows:
+    import torch
+    torch.cuda.init()
+    off, lab = csr_rows(cols, n)
+    BRWTDevice.from_rows(off[:1025], lab[: int(off[1024])], m, arity=a.arity).close()  # warm-up
+    BRWTDevice.from_columns(cols[: min(m, 16)], n, a.arity, layout="rows").close()
+    res = {"from_rows": {"s": [], "used": []}, "from_columns": {"s": [], "used": []}}
+    for _ in range(a.reps):
+        for name in ("from_rows", "from_columns"):
+            with LowWater() as lw:
+                t0 = time.perf_counter()
+                built = (BRWTDevice.from_rows(off, lab, m, arity=a.arity) if name == "from_rows" else
+                         BRWTDevice.from_columns(cols, n, a.arity, layout="rows"))
+                res[name]["s"].append(time.perf_counter() - t0)
+            res[name]["used"].append(int(lw.before - lw.low))
+            res[name]["image_bytes"] = int(built.device_bytes())
+            res[name]["stats"] = built.rows_stats()
+            if name == "from_rows":
+                rows = np.random.default_rng(1).integers(0, n, 200_000).astype(np.uint64)
+                got = built.get_rows(rows)
+            else:
+                want = built.get_rows(rows)
+            built.close()
+    same = (res["from_rows"]["image_bytes"] == res["from_columns"]["image_bytes"]
+            and res["from_rows"]["stats"] == res["from_columns"]["stats"]
+            and all(np.array_equal(x, y) for x, y in zip(got, want)))
+    print(json.dumps({
+        "metric": "row-record build from host data to a queryable context: from_rows (CSR rows) against "
+                  "from_columns(layout='rows') (dense columns), reps alternating in one process",
+        "config": {"rows": n, "columns": m, "density": a.density, "arity": a.arity, "relations": int(len(lab))},
+        **{name: {"median_s": float(np.median(r["s"])), "runs_s": r["s"], "image_bytes": r["image_bytes"],
+                  "device_low_water_used_bytes": int(max(r["used"])), "low_water_runs": r["used"]}
+           for name, r in res.items()},
+        "parity": ("equal image bytes and rows_stats, identical get_rows on 200,000 rows" if same else "MISMATCH"),
+    }))
+    sys.exit(0 if same else 1)
 
 BRWTDevice.from_columns(cols[: min(m, 16)], n, a.arity).close()  # warm-up (HIP init, kernels)
 dev_s = []
