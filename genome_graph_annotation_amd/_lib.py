@@ -143,6 +143,10 @@ SIGNATURES = {
     "mbrwt_create_from_rows": (C.c_int, [C.POINTER(RowsDesc), C.POINTER(ShapeDesc), C.c_uint32, C.c_int,
                                          C.POINTER(C.c_void_p)]),
     "mbrwt_tree_basic_shape": (C.c_int, [C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "mbrwt_rows_node_counts": (C.c_int, [C.POINTER(RowsDesc), C.POINTER(ShapeDesc), C.c_uint32, C.c_int, u64p]),
+    "mbrwt_tree_relax_shape": (C.c_int, [C.POINTER(ShapeDesc), u64p, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "mbrwt_tree_shape_from_rows": (C.c_int, [C.POINTER(RowsDesc), C.c_int, C.c_uint32, C.c_uint64, C.c_int,
+                                             C.POINTER(C.c_void_p)]),
     "mbrwt_create_relaxed": (C.c_int, [C.POINTER(TreeDesc), C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]),
     "mbrwt_get_labels_batch": (C.c_int, [C.c_void_p, u64p, C.c_uint64, u64p, C.c_uint64, C.c_double, u64p, u32p,
                                          C.c_uint64, u64p]),

@@ -178,6 +178,80 @@ def basic_shape(num_columns, arity):
     return dict(num_children=t["num_children"], first_child=t["first_child"], leaf_column=t["leaf_column"])
 
 
+def _shape_dict(handle):
+    t = _tree_dict(handle)
+    return dict(num_children=t["num_children"], first_child=t["first_child"], leaf_column=t["leaf_column"])
+
+
+def _rows_desc(offsets, cols, num_columns):
+    """mbrwt_rows_desc of a CSR and the arrays it points into."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if off.size == 0:
+        raise ValueError("offsets needs num_rows + 1 entries")
+    cl = np.ascontiguousarray(cols, dtype=np.uint32)
+    if cl.size == 0:
+        cl = np.zeros(1, dtype=np.uint32)
+    return L.RowsDesc(off.size - 1, int(num_columns), _p(off, C.c_uint64), _p(cl, C.c_uint32)), (off, cl)
+
+
+def _shape_desc(shape):
+    """mbrwt_shape_desc of a shape dict and the arrays it points into."""
+    nc = np.ascontiguousarray(shape["num_children"], dtype=np.uint32)
+    fc = np.ascontiguousarray(shape["first_child"], dtype=np.uint32)
+    lc = np.ascontiguousarray(shape["leaf_column"], dtype=np.uint32)
+    return L.ShapeDesc(len(nc), _p(nc, C.c_uint32), _p(fc, C.c_uint32), _p(lc, C.c_uint32)), (nc, fc, lc)
+
+
+def node_counts_from_rows(offsets, cols, num_columns, shape=None, arity=8, device=0):
+    """Per BFS node of `shape` (None: basic_shape(num_columns, arity)) the
+    number of CSR rows with a label below it (mbrwt_rows_node_counts): a
+    leaf's column popcount, the root's non-empty rows.  uint64 array."""
+    d, keep = _rows_desc(offsets, cols, num_columns)
+    sd, keep_s = None, None
+    if shape is not None:
+        s, keep_s = _shape_desc(shape)
+        sd = C.byref(s)
+        nodes = len(keep_s[0])
+    else:
+        nodes = len(basic_shape(num_columns, arity)["num_children"])
+    counts = np.zeros(max(1, nodes), dtype=np.uint64)
+    L.check(L.lib().mbrwt_rows_node_counts(C.byref(d), sd, int(arity), device, _p(counts, C.c_uint64)),
+            "mbrwt_rows_node_counts")
+    del keep, keep_s
+    return counts[:nodes]
+
+
+def relax_shape(shape, counts, max_arity):
+    """BRWTOptimizer::relax(max_arity) of a shape dict given the per-node row
+    counts of node_counts_from_rows (mbrwt_tree_relax_shape; host only)."""
+    s, keep = _shape_desc(shape)
+    cn = np.ascontiguousarray(counts, dtype=np.uint64)
+    if cn.size < len(keep[0]):
+        raise ValueError("counts needs one entry per node")
+    if cn.size == 0:
+        cn = np.zeros(1, dtype=np.uint64)
+    h = C.c_void_p()
+    L.check(L.lib().mbrwt_tree_relax_shape(C.byref(s), _p(cn, C.c_uint64), int(max_arity), C.byref(h)),
+            "mbrwt_tree_relax_shape")
+    del keep
+    return _shape_dict(h)
+
+
+def shape_from_rows(offsets, cols, num_columns, partitioner="basic", arity=8, relax_max_arity=0, device=0):
+    """The shape the reference's builders give on the matrix of these CSR rows
+    (mbrwt_tree_shape_from_rows): partitioner 'basic' (of `arity`) or 'greedy'
+    (binary_grouping_greedy over the row sample), then BRWTOptimizer::relax
+    over all rows when relax_max_arity > 1.  Returns the shape dict
+    BRWTDevice.from_rows and BRWTDevice.synthetic_shaped take."""
+    d, keep = _rows_desc(offsets, cols, num_columns)
+    part = L.PARTITIONERS[partitioner] if isinstance(partitioner, str) else int(partitioner)
+    h = C.c_void_p()
+    L.check(L.lib().mbrwt_tree_shape_from_rows(C.byref(d), part, int(arity), int(relax_max_arity), device,
+                                               C.byref(h)), "mbrwt_tree_shape_from_rows")
+    del keep
+    return _shape_dict(h)
+
+
 @contextlib.contextmanager
 def build_layout(layout):
     """Device layout of the contexts created inside the block (None: the
@@ -284,13 +358,22 @@ class BRWTDevice:
         return cls(h)
 
     @classmethod
-    def from_rows(cls, offsets, cols, num_columns, arity=8, shape=None, device=0):
+    def from_rows(cls, offsets, cols, num_columns, arity=8, shape=None, device=0, partitioner="basic",
+                  relax_max_arity=0):
         """Row records straight from CSR rows (mbrwt_create_from_rows): row r
         carries the columns cols[offsets[r]:offsets[r + 1]] (a set, any
         order).  `shape` = dict with num_children, first_child, leaf_column
-        (BFS; e.g. the export of a tree built from a row sample), or None for
-        the basic partitioner's tree of `arity` (basic_shape).  No node image
-        and no dense column is built; the context's layout is 'rows'."""
+        (BFS; e.g. shape_from_rows of the same rows), or None for the basic
+        partitioner's tree of `arity` (basic_shape).  partitioner='greedy' or
+        relax_max_arity > 1: the shape is shape_from_rows(...) of these rows
+        (not together with `shape`).  No node image and no dense column is
+        built; the context's layout is 'rows'."""
+        if partitioner != "basic" or relax_max_arity:
+            if shape is not None:
+                raise ValueError("give a shape, or a partitioner / relax_max_arity to compute one: not both")
+            shape = shape_from_rows(offsets, cols, num_columns, partitioner, arity, relax_max_arity, device)
+            if len(shape["num_children"]) == 0:  # no column: the call below builds the empty context
+                shape = None
         lib = L.lib()
         off = np.ascontiguousarray(offsets, dtype=np.uint64)
         if off.size == 0:

@@ -183,7 +183,8 @@ class BRWTDevice : public BinaryMatrix {
     // = cols[offsets[r] .. offsets[r+1]), a set in any order -- what the
     // reference's annotators produce row by row (annotate_row, RowCompressed).
     // shape == nullptr: the basic partitioner's tree of `arity`; else the
-    // given shape, e.g. that of a greedy + relaxed build of a row sample
+    // given shape, e.g. mbrwt_tree_shape_from_rows of the same rows
+    // (build_from_rows_greedy)
     static BRWTDevice build_from_rows(const std::vector<uint64_t> &offsets, const std::vector<uint32_t> &cols,
                                       uint64_t num_columns, uint32_t arity = 8,
                                       const mbrwt_shape_desc *shape = nullptr, int device = 0) {
@@ -194,6 +195,23 @@ class BRWTDevice : public BinaryMatrix {
         check_status(mbrwt_create_from_rows(&d, shape, arity, device, &c), "mbrwt_create_from_rows");
         m.ctx_.reset(c, Deleter());
         return m;
+    }
+
+    // The reference's production tree (binary_grouping_greedy, then relax when
+    // relax_max_arity > 1) straight from row-major data: the shape from the
+    // rows (mbrwt_tree_shape_from_rows), then their records under it -- what
+    // `transform_anno --greedy` + `relax_brwt` give, with no dense column
+    static BRWTDevice build_from_rows_greedy(const std::vector<uint64_t> &offsets, const std::vector<uint32_t> &cols,
+                                             uint64_t num_columns, uint64_t relax_max_arity = 0, int device = 0) {
+        if (offsets.empty()) throw std::invalid_argument("build_from_rows_greedy: offsets needs num_rows + 1 entries");
+        const mbrwt_rows_desc d{offsets.size() - 1, num_columns, offsets.data(), cols.data()};
+        mbrwt_tree *t = nullptr;
+        check_status(mbrwt_tree_shape_from_rows(&d, MBRWT_PARTITIONER_GREEDY, 2, relax_max_arity, device, &t),
+                     "mbrwt_tree_shape_from_rows");
+        std::unique_ptr<mbrwt_tree, void (*)(mbrwt_tree *)> owned(t, mbrwt_tree_free);
+        const mbrwt_tree_desc *td = mbrwt_tree_get_desc(t);
+        const mbrwt_shape_desc shape{td->num_nodes, td->num_children, td->first_child, td->leaf_column};
+        return build_from_rows(offsets, cols, num_columns, 2, td->num_nodes ? &shape : nullptr, device);
     }
 
     // a query handle over the same device image (mbrwt_ctx_clone): one per

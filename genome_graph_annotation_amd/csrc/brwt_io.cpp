@@ -909,6 +909,22 @@ int export_rows(const Ctx &c, mbrwt_tree &out) {
 }
 
 }  // namespace
+
+// an owned shape-only tree (vec_size 0, num_rows 0) from BFS arrays
+int shape_only_tree(uint64_t num_columns, std::vector<uint32_t> num_children, std::vector<uint32_t> first_child,
+                    std::vector<uint32_t> leaf_column, mbrwt_tree **out) {
+    auto t = std::make_unique<mbrwt_tree>();
+    t->num_columns = num_columns;
+    t->num_children = std::move(num_children);
+    t->first_child = std::move(first_child);
+    t->leaf_column = std::move(leaf_column);
+    t->vec_size.assign(t->num_children.size(), 0);
+    t->words.resize(t->num_children.size());
+    t->finish();
+    *out = t.release();
+    return MBRWT_OK;
+}
+
 }  // namespace mbrwt
 
 using namespace mbrwt;
@@ -1042,15 +1058,10 @@ int mbrwt_tree_basic_shape(uint64_t num_columns, uint32_t arity, mbrwt_tree **ou
     }
     *out = nullptr;
     try {
-        auto t = std::make_unique<mbrwt_tree>();
-        t->num_columns = num_columns;
-        const int rc = basic_shape(num_columns, arity, t->num_children, t->first_child, t->leaf_column);
+        std::vector<uint32_t> nc, fc, lc;
+        const int rc = basic_shape(num_columns, arity, nc, fc, lc);
         if (rc) return rc;
-        t->vec_size.assign(t->num_children.size(), 0);
-        t->words.resize(t->num_children.size());
-        t->finish();
-        *out = t.release();
-        return MBRWT_OK;
+        return shape_only_tree(num_columns, std::move(nc), std::move(fc), std::move(lc), out);
     } catch (const std::bad_alloc &) {
         set_error("out of host memory");
         return MBRWT_ERR_NOMEM;

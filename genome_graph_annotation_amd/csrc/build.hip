@@ -253,6 +253,80 @@ std::vector<std::vector<size_t>> greedy_groups(const std::vector<uint32_t> &sim,
     return groups;
 }
 
+// One level of the greedy partitioner over "the level's sample columns": L
+// columns of SW sample words each (d_simcols: their L device pointers, on the
+// device) -> the level's groups.  The products are computed on the device and
+// matched on the host; both builders -- from columns (desc_from_columns) and
+// from rows (greedy_shape_from_rows) -- partition their levels here.
+int greedy_level(const uint64_t *const *d_simcols, size_t L, uint64_t SW, hipStream_t s,
+                 std::vector<std::vector<size_t>> &part, double &sim_ms, double &sort_ms) {
+    if ((uint64_t)L * (L - 1) / 2 > (1ull << 31)) {
+        // the reference keeps every pair as a candidate too
+        // (partitionings.cpp:154-160): > 2^31 pairs is > 50 GB of host
+        // candidates -- refuse instead of exhausting the host
+        set_error("greedy partitioner: more than 65,536 columns on one level");
+        return MBRWT_ERR_UNSUPPORTED;
+    }
+    const uint64_t T = (L + kSimTile - 1) / kSimTile, tiles = T * (T + 1) / 2;
+    if (tiles > 0x7FFFFFFFull) {
+        set_error("too many columns for the greedy partitioner");
+        return MBRWT_ERR_UNSUPPORTED;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t npairs = (uint64_t)L * (L - 1) / 2;
+    uint32_t *d_sim = nullptr;
+    if (hipMalloc(&d_sim, std::max<size_t>(npairs * sizeof(uint32_t), 8)) != hipSuccess)
+        return hip_fail(hipErrorOutOfMemory, "builder allocation");
+    std::vector<uint32_t> sim(npairs);
+    hipLaunchKernelGGL(k_similarity, dim3((unsigned)tiles), dim3(256), 0, s, d_simcols, (uint32_t)L, SW, d_sim);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(sim.data(), d_sim, npairs * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(d_sim);
+    if (e != hipSuccess) return hip_fail(e, "greedy partitioner: similarities");
+    const auto t1 = std::chrono::steady_clock::now();
+    part = greedy_groups(sim, L);
+    const auto t2 = std::chrono::steady_clock::now();
+    sim_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    sort_ms += std::chrono::duration<double, std::milli>(t2 - t1).count();
+    return MBRWT_OK;
+}
+
+// ---- the greedy shape from row-major data -------------------
+//
+// The similarity of two nodes is the number of sampled rows with a label
+// below both, so the partitioner needs the sample's columns and nothing else
+// of the matrix: the sampled rows, gathered from the host CSR, are scattered
+// into m zeroed sample columns (k_sample_scatter), and a parent's sample
+// column is the OR of its children's (k_or_words).
+
+// bit s of sample column c for every label c of sampled row s (one lane per row)
+__global__ __launch_bounds__(256) void k_sample_scatter(const uint64_t *__restrict__ off, uint64_t ns,
+                                                        const uint32_t *__restrict__ cols, uint64_t m, uint64_t SW,
+                                                        unsigned long long *samp) {
+    const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < ns; r += gs) {
+        const uint64_t a = gld(off + r), b = gld(off + r + 1);
+        for (uint64_t p = a; p < b; ++p) {
+            const uint64_t c = gld(cols + p);
+            if (c < m) atomicOr(samp + c * SW + (r >> 6), 1ull << (r & 63));  // (the host checked the columns)
+        }
+    }
+}
+
+// parents[g][w] = OR of the sample words of group g's children (g = y0 + blockIdx.y)
+__global__ __launch_bounds__(256) void k_or_words(const uint64_t *const *child_col, const uint32_t *gchild,
+                                                  uint64_t *parents, uint64_t SW, uint32_t y0) {
+    const uint32_t g = y0 + blockIdx.y;
+    const uint32_t c0 = gchild[g], c1 = gchild[g + 1];
+    const uint64_t gstride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < SW; w += gstride) {
+        uint64_t x = 0;
+        for (uint32_t c = c0; c < c1; ++c) x |= gld(child_col[c] + w);
+        parents[(uint64_t)g * SW + w] = x;
+    }
+}
+
 // ---- BRWTOptimizer::relax (BRWT_builders.cpp:166-297) ----------------------
 //
 // reassign (:257-297) moves a pruned node's children up to its parent: a
@@ -314,18 +388,57 @@ uint64_t popcount_words(const std::vector<uint64_t> &v, uint64_t len) {
     return c;
 }
 
-int relax_nodes(std::vector<BNode> &nodes, uint32_t root, uint64_t max_arity, hipStream_t s) {
-    std::vector<uint64_t> ones(nodes.size());
-    for (size_t u = 0; u < nodes.size(); ++u) ones[u] = popcount_words(nodes[u].index, nodes[u].index_len);
+// The DECISIONS of relax (:166-255, :351-380) over two numbers per node: the
+// length of its index column, len(u), and the bits set in it, ones[u] --
+// reassign preserves the latter.  kids(u): the node's children (a
+// std::vector<uint32_t> &, rewritten here); reassign(u) moves the pruned node
+// u's children up to its parent -- after it len(c) == len(u) for every child
+// c of u -- and is all that touches index columns, where there are any.
+template <class Kids, class Len, class Reassign>
+int relax_decide(uint32_t root, uint64_t max_arity, const std::vector<uint64_t> &ones, Kids &&kids, Len &&len,
+                 Reassign &&reassign) {
     // pruning_delta (:351-380)
     auto delta = [&](uint32_t u) {
         double d = 0;
-        for (uint32_t c : nodes[u].children) {
-            d += bv_space_taken_rrr63(nodes[u].index_len, ones[c]);
-            d -= bv_space_taken_rrr63(nodes[c].index_len, ones[c]);
+        for (uint32_t c : kids(u)) {
+            d += bv_space_taken_rrr63(len(u), ones[c]);
+            d -= bv_space_taken_rrr63(len(c), ones[c]);
         }
-        return d - bv_space_taken_rrr63(nodes[u].index_len, ones[u]);
+        return d - bv_space_taken_rrr63(len(u), ones[u]);
     };
+    // parents in BFT order, pushed to the front: leaves' parents first, root last (:171-179)
+    std::vector<uint32_t> bft{root};
+    for (size_t h = 0; h < bft.size(); ++h)
+        for (uint32_t c : kids(bft[h])) bft.push_back(c);
+    for (auto it = bft.rbegin(); it != bft.rend(); ++it) {
+        if (kids(*it).empty()) continue;
+        const std::vector<uint32_t> old = kids(*it);
+        std::vector<uint32_t> updated;
+        const uint64_t nchild = old.size();
+        for (uint64_t g = 0; g < nchild; ++g) {
+            const uint32_t c = old[g];
+            // add_submatrix (:213-255): the arity budget left for this child
+            const uint64_t used = updated.size() + nchild - g - 1;
+            const uint64_t max_delta = max_arity - std::min<uint64_t>(max_arity, used);
+            bool prune = !kids(c).empty();
+            if (prune && kids(c).size() > max_delta) prune = false;
+            if (!prune || delta(c) > 0) {
+                updated.push_back(c);
+            } else {
+                int rc = reassign(c);
+                if (rc) return rc;
+                for (uint32_t gc : kids(c)) updated.push_back(gc);
+                kids(c).clear();
+            }
+        }
+        kids(*it) = std::move(updated);
+    }
+    return MBRWT_OK;
+}
+
+int relax_nodes(std::vector<BNode> &nodes, uint32_t root, uint64_t max_arity, hipStream_t s) {
+    std::vector<uint64_t> ones(nodes.size());
+    for (size_t u = 0; u < nodes.size(); ++u) ones[u] = popcount_words(nodes[u].index, nodes[u].index_len);
     // reassign (:257-297) on the device
     auto reassign = [&](uint32_t u) -> int {
         BNode &node = nodes[u];
@@ -399,54 +512,47 @@ int relax_nodes(std::vector<BNode> &nodes, uint32_t root, uint64_t max_arity, hi
         set_error("relax: HIP error while expanding index columns");
         return MBRWT_ERR_DEVICE;
     };
-    // parents in BFT order, pushed to the front: leaves' parents first, root last (:171-179)
-    std::vector<uint32_t> bft{root};
-    for (size_t h = 0; h < bft.size(); ++h)
-        for (uint32_t c : nodes[bft[h]].children) bft.push_back(c);
-    for (auto it = bft.rbegin(); it != bft.rend(); ++it) {
-        BNode &parent = nodes[*it];
-        if (parent.children.empty()) continue;
-        const std::vector<uint32_t> old = parent.children;
-        std::vector<uint32_t> updated;
-        const uint64_t nchild = old.size();
-        for (uint64_t g = 0; g < nchild; ++g) {
-            const uint32_t c = old[g];
-            // add_submatrix (:213-255): the arity budget left for this child
-            const uint64_t used = updated.size() + nchild - g - 1;
-            const uint64_t max_delta = max_arity - std::min<uint64_t>(max_arity, used);
-            bool prune = !nodes[c].children.empty();
-            if (prune && nodes[c].children.size() > max_delta) prune = false;
-            if (!prune || delta(c) > 0) {
-                updated.push_back(c);
-            } else {
-                int rc = reassign(c);
-                if (rc) return rc;
-                for (uint32_t gc : nodes[c].children) updated.push_back(gc);
-                nodes[c].children.clear();
-                nodes[c].index.clear();
-            }
-        }
-        nodes[*it].children = std::move(updated);
-    }
-    return MBRWT_OK;
+    return relax_decide(
+        root, max_arity, ones, [&](uint32_t u) -> std::vector<uint32_t> & { return nodes[u].children; },
+        [&](uint32_t u) { return nodes[u].index_len; },
+        [&](uint32_t u) {
+            const int rc = reassign(u);
+            if (!rc) nodes[u].index.clear();
+            return rc;
+        });
 }
 
-// breadth-first numbering of the node tree (mbrwt_tree_desc) and the image
-int desc_from_nodes(const std::vector<BNode> &nodes, uint32_t root, uint64_t n, uint64_t m, const DescSink &emit) {
+// breadth-first numbering of the node tree from its root: the nodes in BFS
+// order and the shape's BFS arrays (mbrwt_shape_desc)
+std::vector<uint32_t> bfs_shape(const std::vector<BNode> &nodes, uint32_t root, std::vector<uint32_t> &num_children,
+                                std::vector<uint32_t> &first_child, std::vector<uint32_t> &leaf_column) {
     std::vector<uint32_t> order{root};
     for (size_t h = 0; h < order.size(); ++h)
         for (uint32_t c : nodes[order[h]].children) order.push_back(c);
     const uint32_t N = (uint32_t)order.size();
     std::vector<uint32_t> bfs(nodes.size());
     for (uint32_t i = 0; i < N; ++i) bfs[order[i]] = i;
-    std::vector<uint32_t> num_children(N), first_child(N), leaf_column(N);
-    std::vector<uint64_t> vec_size(N);
-    std::vector<const uint64_t *> vec_words(N);
+    num_children.assign(N, 0);
+    first_child.assign(N, 0);
+    leaf_column.assign(N, 0);
     for (uint32_t i = 0; i < N; ++i) {
         const BNode &b = nodes[order[i]];
         num_children[i] = (uint32_t)b.children.size();
         first_child[i] = b.children.empty() ? 0 : bfs[b.children[0]];
         leaf_column[i] = b.children.empty() ? b.column : UINT32_MAX;
+    }
+    return order;
+}
+
+// the node tree as an mbrwt_tree_desc, and the image
+int desc_from_nodes(const std::vector<BNode> &nodes, uint32_t root, uint64_t n, uint64_t m, const DescSink &emit) {
+    std::vector<uint32_t> num_children, first_child, leaf_column;
+    const std::vector<uint32_t> order = bfs_shape(nodes, root, num_children, first_child, leaf_column);
+    const uint32_t N = (uint32_t)order.size();
+    std::vector<uint64_t> vec_size(N);
+    std::vector<const uint64_t *> vec_words(N);
+    for (uint32_t i = 0; i < N; ++i) {
+        const BNode &b = nodes[order[i]];
         vec_size[i] = b.index_len;
         vec_words[i] = b.index.data();
     }
@@ -578,23 +684,14 @@ int desc_from_columns(const mbrwt_columns_desc &cd, int device, hipStream_t s, u
             }
         } else {
             const size_t L = level.size();
-            if ((uint64_t)L * (L - 1) / 2 > (1ull << 31)) {
-                // the reference keeps every pair as a candidate too
-                // (partitionings.cpp:154-160): > 2^31 pairs is > 50 GB of host
-                // candidates -- refuse instead of exhausting the host
-                cleanup();
-                set_error("greedy partitioner: more than 65,536 columns on one level");
-                return MBRWT_ERR_UNSUPPORTED;
-            }
             const auto t0 = std::chrono::steady_clock::now();
-            // the level's columns (pointer table), the sampled words, the products
+            // the level's sample columns: the row columns themselves (pointer
+            // table) or their sampled words
             std::vector<const uint64_t *> hp(L);
             for (size_t i = 0; i < L; ++i) hp[i] = nodes[level[i]].rowcol;
             const uint64_t **d_ptr = reinterpret_cast<const uint64_t **>(dalloc(L * sizeof(void *) * 2));
             uint64_t *d_sub = sample_all ? nullptr : reinterpret_cast<uint64_t *>(dalloc(L * SW * sizeof(uint64_t)));
-            const uint64_t npairs = (uint64_t)L * (L - 1) / 2;
-            uint32_t *d_sim = reinterpret_cast<uint32_t *>(dalloc(npairs * sizeof(uint32_t)));
-            if (!d_ptr || (!sample_all && !d_sub) || !d_sim) {
+            if (!d_ptr || (!sample_all && !d_sub)) {
                 cleanup();
                 return hip_fail(hipErrorOutOfMemory, "builder allocation");
             }
@@ -612,23 +709,12 @@ int desc_from_columns(const mbrwt_columns_desc &cd, int device, hipStream_t s, u
                 MBRWT_HIP(hipMemcpyAsync(d_ptr + L, hs.data(), L * sizeof(void *), hipMemcpyHostToDevice, s));
                 simcols = d_ptr + L;
             }
-            const uint64_t T = (L + kSimTile - 1) / kSimTile, tiles = T * (T + 1) / 2;
-            if (tiles > 0x7FFFFFFFull) {
+            // (the gather runs on the stream: its time is in the level's similarities)
+            t_sim_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            if (const int rc = greedy_level(simcols, L, SW, s, part, t_sim_ms, t_sort_ms)) {
                 cleanup();
-                set_error("too many columns for the greedy partitioner");
-                return MBRWT_ERR_UNSUPPORTED;
+                return rc;
             }
-            hipLaunchKernelGGL(k_similarity, dim3((unsigned)tiles), dim3(256), 0, s, simcols, (uint32_t)L, SW, d_sim);
-            MBRWT_HIP(hipGetLastError());
-            std::vector<uint32_t> sim(npairs);
-            MBRWT_HIP(hipMemcpyAsync(sim.data(), d_sim, npairs * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            MBRWT_HIP(hipStreamSynchronize(s));
-            const auto t1 = std::chrono::steady_clock::now();
-            part = greedy_groups(sim, L);
-            const auto t2 = std::chrono::steady_clock::now();
-            t_sim_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
-            t_sort_ms += std::chrono::duration<double, std::milli>(t2 - t1).count();
-            dfree(d_sim);
             if (d_sub) dfree(d_sub);
             dfree(d_ptr);
         }
@@ -818,6 +904,208 @@ int relaxed_desc(const mbrwt_tree_desc &desc, uint64_t max_arity, int device, hi
     const int rc = relax_nodes(nodes, 0, max_arity, s);
     if (rc) return rc;
     return desc_from_nodes(nodes, 0, desc.num_rows, desc.num_columns, emit);
+}
+
+// BRWTOptimizer::relax over per-node row counts: with
+// cnt(u) = the rows with a label below u, node u's index column has
+// cnt(parent(u)) bits of which cnt(u) are set, and reassign hands the pruned
+// node's length to its children -- the decisions need nothing else.  (The
+// root's own length, the number of rows, enters no decision: only children of
+// a visited parent are pruned.)  Host only.
+int relax_shape(const mbrwt_shape_desc &shape, const uint64_t *counts, uint64_t max_arity,
+                std::vector<uint32_t> &num_children, std::vector<uint32_t> &first_child,
+                std::vector<uint32_t> &leaf_column) {
+    const uint32_t N = shape.num_nodes;
+    if (N && (!shape.num_children || !shape.first_child || !shape.leaf_column)) {
+        set_error("null array in shape description");
+        return MBRWT_ERR_INVALID;
+    }
+    if (!N || max_arity <= 1) {
+        num_children.assign(shape.num_children, shape.num_children + N);
+        first_child.assign(shape.first_child, shape.first_child + N);
+        leaf_column.assign(shape.leaf_column, shape.leaf_column + N);
+        return MBRWT_OK;
+    }
+    std::vector<BNode> nodes(N);
+    std::vector<uint64_t> ones(counts, counts + N);
+    std::vector<uint8_t> seen(N, 0);
+    for (uint32_t u = 0; u < N; ++u) {
+        const uint32_t k = shape.num_children[u];
+        if (k && ((uint64_t)shape.first_child[u] + k > N || shape.first_child[u] <= u)) {
+            set_error("children not in BFS order");
+            return MBRWT_ERR_INVALID;
+        }
+        nodes[u].column = k ? UINT32_MAX : shape.leaf_column[u];
+        for (uint32_t i = 0; i < k; ++i) {
+            const uint32_t c = shape.first_child[u] + i;
+            if (seen[c]++) {
+                set_error("node has two parents");
+                return MBRWT_ERR_INVALID;
+            }
+            nodes[u].children.push_back(c);
+            nodes[c].index_len = counts[u];
+        }
+    }
+    const int rc = relax_decide(
+        0, max_arity, ones, [&](uint32_t u) -> std::vector<uint32_t> & { return nodes[u].children; },
+        [&](uint32_t u) { return nodes[u].index_len; },
+        [&](uint32_t u) {
+            for (uint32_t c : nodes[u].children) nodes[c].index_len = nodes[u].index_len;
+            return (int)MBRWT_OK;
+        });
+    if (rc) return rc;
+    bfs_shape(nodes, 0, num_children, first_child, leaf_column);
+    return MBRWT_OK;
+}
+
+int greedy_shape_from_rows(const mbrwt_rows_desc &desc, int device, std::vector<uint32_t> &num_children,
+                           std::vector<uint32_t> &first_child, std::vector<uint32_t> &leaf_column) {
+    num_children.clear();
+    first_child.clear();
+    leaf_column.clear();
+    const uint64_t n = desc.num_rows, m = desc.num_columns;
+    if (m > 0xFFFFFFFFull) {
+        set_error("num_columns >= 2^32 is not supported by this build");
+        return MBRWT_ERR_UNSUPPORTED;
+    }
+    if (m == 0) return MBRWT_OK;
+    // the sample (every row, in order, up to 10^6 rows) as a small CSR; its
+    // rows are checked here: a column out of range, a column twice in a row
+    std::vector<uint64_t> sample;
+    const bool sample_all = n <= 1000000;
+    if (!sample_all) sample = greedy_sample_rows(n);
+    const uint64_t ns = sample_all ? n : sample.size(), SW = (ns + 63) / 64;
+    std::vector<uint64_t> soff(ns + 1, 0);
+    std::vector<uint32_t> scols;
+    {
+        std::vector<uint64_t> seen(m, 0);  // the last sampled row (+ 1) that held the column
+        for (uint64_t k = 0; k < ns; ++k) {
+            const uint64_t r = sample_all ? k : sample[k];
+            for (uint64_t p = desc.offsets[r]; p < desc.offsets[r + 1]; ++p) {
+                const uint32_t c = desc.cols[p];
+                if (c >= m) {
+                    set_error("column id >= num_columns");
+                    return MBRWT_ERR_INVALID;
+                }
+                if (seen[c] == k + 1) {
+                    set_error("a column listed twice in a row");
+                    return MBRWT_ERR_INVALID;
+                }
+                seen[c] = k + 1;
+            }
+            scols.insert(scols.end(), desc.cols + desc.offsets[r], desc.cols + desc.offsets[r + 1]);
+            soff[k + 1] = scols.size();
+        }
+    }
+    if (m == 1) {  // the single leaf
+        num_children.assign(1, 0);
+        first_child.assign(1, 0);
+        leaf_column.assign(1, 0);
+        return MBRWT_OK;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        set_error("no HIP device available");
+        return MBRWT_ERR_DEVICE;
+    }
+    if (device < 0 || device >= ndev) {
+        set_error("device index out of range");
+        return MBRWT_ERR_INVALID;
+    }
+    MBRWT_HIP(hipSetDevice(device));
+    struct Scope {
+        hipStream_t s = nullptr;
+        std::vector<void *> allocs;
+        void *alloc(size_t bytes) {
+            void *p = nullptr;
+            if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
+            allocs.push_back(p);
+            return p;
+        }
+        ~Scope() {
+            if (s) (void)hipStreamSynchronize(s);
+            for (void *p : allocs) (void)hipFree(p);
+            if (s) (void)hipStreamDestroy(s);
+        }
+    } sc;
+    MBRWT_HIP(hipStreamCreateWithFlags(&sc.s, hipStreamNonBlocking));
+    hipStream_t s = sc.s;
+    uint64_t *d_off = reinterpret_cast<uint64_t *>(sc.alloc((ns + 1) * sizeof(uint64_t)));
+    uint32_t *d_scols = reinterpret_cast<uint32_t *>(sc.alloc(scols.size() * sizeof(uint32_t)));
+    uint64_t *d_samp = reinterpret_cast<uint64_t *>(sc.alloc(m * SW * sizeof(uint64_t)));
+    if (!d_off || !d_scols || !d_samp) return hip_fail(hipErrorOutOfMemory, "builder allocation");
+    MBRWT_HIP(hipMemcpyAsync(d_off, soff.data(), (ns + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    if (!scols.empty())
+        MBRWT_HIP(hipMemcpyAsync(d_scols, scols.data(), scols.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    MBRWT_HIP(hipMemsetAsync(d_samp, 0, std::max<uint64_t>(m * SW * sizeof(uint64_t), 8), s));
+    if (ns) {
+        hipLaunchKernelGGL(k_sample_scatter, dim3(grid256(ns)), dim3(256), 0, s, d_off, ns, d_scols, m, SW,
+                           reinterpret_cast<unsigned long long *>(d_samp));
+        MBRWT_HIP(hipGetLastError());
+    }
+    std::vector<BNode> nodes(m);
+    std::vector<uint32_t> level(m);
+    for (uint32_t j = 0; j < m; ++j) {
+        nodes[j].column = j;
+        nodes[j].rowcol = d_samp + (uint64_t)j * SW;  // (here: the node's SAMPLE column)
+        level[j] = j;
+    }
+    double sim_ms = 0, sort_ms = 0;
+    while (level.size() > 1) {
+        const size_t L = level.size();
+        std::vector<const uint64_t *> hp(L);
+        for (size_t i = 0; i < L; ++i) hp[i] = nodes[level[i]].rowcol;
+        const uint64_t **d_ptr = reinterpret_cast<const uint64_t **>(sc.alloc(L * sizeof(void *)));
+        if (!d_ptr) return hip_fail(hipErrorOutOfMemory, "builder allocation");
+        MBRWT_HIP(hipMemcpyAsync(d_ptr, hp.data(), L * sizeof(void *), hipMemcpyHostToDevice, s));
+        std::vector<std::vector<size_t>> part;
+        if (const int rc = greedy_level(d_ptr, L, SW, s, part, sim_ms, sort_ms)) return rc;
+        // the pairs' parents: their sample columns are the OR of their
+        // children's; a group of one passes through with its own
+        std::vector<uint32_t> next, gchild{0};
+        std::vector<const uint64_t *> child_col;
+        std::vector<size_t> group_slot;
+        for (const auto &grp : part) {
+            if (grp.size() == 1) {
+                next.push_back(level[grp[0]]);
+                continue;
+            }
+            BNode parent;
+            for (const size_t i : grp) {  // (the group's order: the reference's child order)
+                parent.children.push_back(level[i]);
+                child_col.push_back(nodes[level[i]].rowcol);
+            }
+            gchild.push_back((uint32_t)child_col.size());
+            group_slot.push_back(next.size());
+            next.push_back((uint32_t)nodes.size());
+            nodes.push_back(std::move(parent));
+        }
+        const uint32_t G = (uint32_t)group_slot.size();
+        if (next.size() > 1) {  // (the root's sample column is never read)
+            uint64_t *d_par = reinterpret_cast<uint64_t *>(sc.alloc(G * SW * sizeof(uint64_t)));
+            const uint64_t **d_child = reinterpret_cast<const uint64_t **>(sc.alloc(child_col.size() * sizeof(void *)));
+            uint32_t *d_gchild = reinterpret_cast<uint32_t *>(sc.alloc((G + 1) * sizeof(uint32_t)));
+            if (!d_par || !d_child || !d_gchild) return hip_fail(hipErrorOutOfMemory, "builder allocation");
+            MBRWT_HIP(hipMemcpyAsync(d_child, child_col.data(), child_col.size() * sizeof(void *),
+                                     hipMemcpyHostToDevice, s));
+            MBRWT_HIP(hipMemcpyAsync(d_gchild, gchild.data(), (G + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            for (uint32_t y0 = 0; SW && y0 < G; y0 += 65535) {  // grid y <= 65535
+                const uint32_t ny = std::min<uint32_t>(65535, G - y0);
+                hipLaunchKernelGGL(k_or_words, dim3(grid_of(SW, ny), ny), dim3(256), 0, s, d_child, d_gchild, d_par,
+                                   SW, y0);
+            }
+            MBRWT_HIP(hipGetLastError());
+            // (the host tables are pageable: the copies above have read them)
+            MBRWT_HIP(hipStreamSynchronize(s));
+            for (uint32_t g = 0; g < G; ++g) nodes[next[group_slot[g]]].rowcol = d_par + (uint64_t)g * SW;
+        }
+        level.swap(next);
+    }
+    if (const char *e = std::getenv("MBRWT_BUILD_TIMING"); e && e[0] == '1')
+        std::fprintf(stderr, "[mbrwt shape from rows] greedy: similarities %.1f ms, sort + matching %.1f ms\n", sim_ms,
+                     sort_ms);
+    bfs_shape(nodes, level[0], num_children, first_child, leaf_column);
+    return MBRWT_OK;
 }
 
 }  // namespace mbrwt

@@ -368,6 +368,30 @@ static int create_rows_ranged(int device, uint64_t num_rows, uint64_t num_column
 struct RowsFromEnd {
     void operator()(RowsFrom *rf) const { rows_from_end(rf); }
 };
+// the largest range [a, a + k kRowsAlign), k kRowsAlign <= R, of the n rows of
+// `off` whose labels fit the free device memory less the reserve and
+// `pending` (the bytes the build will still allocate); a fixed range size
+// (MBRWT_BUILD_ROWS_RANGE) is taken as it is
+static uint64_t cut_rows_range(const uint64_t *off, uint64_t n, uint64_t a, uint64_t R, uint64_t pending) {
+    uint64_t b = std::min(n, a + R);
+    if (build_tuning().rows_range != 0) return b;
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    const double left = (double)free_b - 8.0 * (1ull << 30) - (double)pending;
+    const double budget = std::max(left, (double)free_b / 8) / 1.2;
+    auto fits = [&](uint64_t e) {
+        const uint64_t L = off[e] - off[a];
+        return L <= kRowsFromMaxLabels && (double)rows_from_range_bytes(e - a, L) <= budget;
+    };
+    if (fits(b)) return b;
+    uint64_t lo = 1, hi = (b - a + kRowsAlign - 1) / kRowsAlign;  // lo: taken whatever it costs
+    while (lo + 1 < hi) {
+        const uint64_t mid = (lo + hi) / 2;
+        (fits(a + mid * kRowsAlign) ? lo : hi) = mid;
+    }
+    return std::min(n, a + lo * kRowsAlign);
+}
+
 static int create_from_rows(const mbrwt_rows_desc &desc, const Tree &shape, int device, mbrwt_ctx **out) {
     const uint64_t n = desc.num_rows;
     const uint64_t *off = desc.offsets;
@@ -383,29 +407,10 @@ static int create_from_rows(const mbrwt_rows_desc &desc, const Tree &shape, int 
             RowsBuildPtr rb(rows_build_begin(c, n, kRowsAlign, false));
             if (!rb) return (int)MBRWT_ERR_NOMEM;
             const bool fixed = build_tuning().rows_range != 0;
-            // the largest range [a, a + k kRowsAlign), k kRowsAlign <= R, within the budget
-            auto cut = [&](uint64_t a, uint64_t R) {
-                uint64_t b = std::min(n, a + R);
-                if (fixed) return b;
-                size_t free_b = 0, total_b = 0;
-                (void)hipMemGetInfo(&free_b, &total_b);
-                const double left = (double)free_b - 8.0 * (1ull << 30) -
-                                    (double)rows_build_pending_bytes(rb.get(), n - a);
-                const double budget = std::max(left, (double)free_b / 8) / 1.2;
-                auto fits = [&](uint64_t e) {
-                    const uint64_t L = off[e] - off[a];
-                    return L <= kRowsFromMaxLabels && (double)rows_from_range_bytes(e - a, L) <= budget;
-                };
-                if (fits(b)) return b;
-                uint64_t lo = 1, hi = (b - a + kRowsAlign - 1) / kRowsAlign;  // lo: taken whatever it costs
-                while (lo + 1 < hi) {
-                    const uint64_t mid = (lo + hi) / 2;
-                    (fits(a + mid * kRowsAlign) ? lo : hi) = mid;
-                }
-                return std::min(n, a + lo * kRowsAlign);
-            };
             for (uint64_t a = 0, b = 0; a < n; a = b) {
-                b = cut(a, fixed || a ? rows_range_rows() : std::min(rows_range_rows(), kRowsFirstRange));
+                b = cut_rows_range(off, n, a,
+                                   fixed || a ? rows_range_rows() : std::min(rows_range_rows(), kRowsFirstRange),
+                                   fixed ? 0 : rows_build_pending_bytes(rb.get(), n - a));
                 if (int rc = rows_from_range(rf.get(), rb.get(), off, desc.cols, a, b, &c.tree.num_relations))
                     return rc;  // (rb frees the build)
             }
@@ -415,6 +420,71 @@ static int create_from_rows(const mbrwt_rows_desc &desc, const Tree &shape, int 
             return (int)MBRWT_OK;
         },
         kNoLayoutHook);
+}
+
+// Per-node row counts of CSR rows under a tree shape (rows_counts.hip;
+// DESIGN.md §11c): the ranges, the upload, the keys and the sort of
+// create_from_rows without any record, so a range takes the memory the
+// records would; the counts accumulate on the device across the ranges and
+// come back once, dnode u + 1 of the shape table being BFS node u.
+static int rows_node_counts(const mbrwt_rows_desc &desc, const Tree &shape, int device, uint64_t *counts) {
+    const uint64_t n = desc.num_rows;
+    const uint64_t *off = desc.offsets;
+    const size_t D = shape.nodes.size();
+    // the walk's limits (rows_emit.hpp emit_label_masks): internal levels on a path
+    std::vector<uint32_t> level(D, 0);
+    for (size_t v = 1; v < D; ++v) {
+        const DevNode &dn = shape.nodes[v];
+        if (dn.kind == KIND_LEAF) continue;
+        if (v == 1) level[v] = 1;
+        if (level[v] > kRowsMaxHeight) {
+            set_error(rows_limits_message());
+            return MBRWT_ERR_UNSUPPORTED;
+        }
+        for (uint32_t c = 0; c < dn.arity; ++c) level[dn.first_child + c] = level[v] + 1;
+    }
+    for (uint64_t r = 0; r < n; ++r)
+        if (off[r + 1] - off[r] > 0x7FFFu) {
+            set_error("row record deeper than the build walker supports, or a row of more than 32,767 labels");
+            return MBRWT_ERR_UNSUPPORTED;
+        }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        set_error("no HIP device available");
+        return MBRWT_ERR_DEVICE;
+    }
+    if (device < 0 || device >= ndev) {
+        set_error("device index out of range");
+        return MBRWT_ERR_INVALID;
+    }
+    MBRWT_HIP(hipSetDevice(device));
+    struct Scope {
+        hipStream_t s = nullptr;
+        unsigned long long *d_counts = nullptr;
+        RowsFrom *rf = nullptr;
+        ~Scope() {
+            rows_from_end(rf);
+            if (d_counts) (void)hipFree(d_counts);
+            if (s) (void)hipStreamDestroy(s);
+        }
+    } sc;
+    MBRWT_HIP(hipStreamCreateWithFlags(&sc.s, hipStreamNonBlocking));
+    if (int rc = rows_from_begin(shape, sc.s, &sc.rf)) return rc;
+    MBRWT_HIP(hipMalloc(&sc.d_counts, D * sizeof(uint64_t)));
+    MBRWT_HIP(hipMemsetAsync(sc.d_counts, 0, D * sizeof(uint64_t), sc.s));
+    for (uint64_t a = 0, b = 0; a < n; a = b) {
+        b = cut_rows_range(off, n, a, rows_range_rows(), 0);
+        LabelRows rows;
+        if (int rc = rows_from_load(sc.rf, off, desc.cols, a, b, &rows)) return rc;
+        if (int rc = rows_counts_range(rows, b - a, (uint32_t)D, sc.d_counts, sc.s)) return rc;
+        // (the next load overwrites the range's buffers)
+        MBRWT_HIP(hipStreamSynchronize(sc.s));
+    }
+    std::vector<unsigned long long> h(D);
+    MBRWT_HIP(hipMemcpyAsync(h.data(), sc.d_counts, D * sizeof(uint64_t), hipMemcpyDeviceToHost, sc.s));
+    MBRWT_HIP(hipStreamSynchronize(sc.s));
+    for (size_t u = 0; u + 1 < D; ++u) counts[u] = h[u + 1];
+    return MBRWT_OK;
 }
 
 // Layouts ROWS and AUTO over many rows build ranged: beyond kAutoRangedRows
@@ -476,6 +546,37 @@ static int create_synthetic_any(const mbrwt_synth_desc &desc, const mbrwt_shape_
             return (int)MBRWT_OK;
         },
         layout);
+}
+
+// the checks of a CSR of num_rows > 0 rows over num_columns > 0 columns that
+// need no device (mbrwt_create_from_rows, mbrwt_rows_node_counts)
+static int check_rows_desc(const mbrwt_rows_desc &d) {
+    const uint64_t n = d.num_rows, m = d.num_columns;
+    if (!d.offsets || d.offsets[0] != 0 || (d.offsets[n] && !d.cols)) {
+        set_error("row offsets: null array or first offset not 0");
+        return MBRWT_ERR_INVALID;
+    }
+    for (uint64_t r = 0; r < n; ++r) {
+        if (d.offsets[r + 1] < d.offsets[r]) {
+            set_error("row offsets not ascending");
+            return MBRWT_ERR_INVALID;
+        }
+        // (rows are sets: more labels than columns repeat one)
+        if (d.offsets[r + 1] - d.offsets[r] > m) {
+            set_error("a row of more labels than columns");
+            return MBRWT_ERR_INVALID;
+        }
+    }
+    return MBRWT_OK;
+}
+
+// the Tree of the caller's shape, or of the basic partitioner's of `arity`
+static int rows_shape_tree(const mbrwt_shape_desc *shape, uint64_t m, uint32_t arity, Tree &tree) {
+    if (shape) return shape_tree(*shape, m, tree);
+    std::vector<uint32_t> nc, fc, lc;
+    if (const int rc = basic_shape(m, arity, nc, fc, lc)) return rc;
+    const mbrwt_shape_desc sd{(uint32_t)nc.size(), nc.data(), fc.data(), lc.data()};
+    return shape_tree(sd, m, tree);
 }
 
 }  // namespace mbrwt
@@ -613,36 +714,104 @@ int mbrwt_create_from_rows(const mbrwt_rows_desc *desc, const mbrwt_shape_desc *
             const mbrwt_columns_desc cd{n, m, none.data(), shape ? 2u : arity};
             return mbrwt_create_from_columns(&cd, device, out);
         }
-        if (!desc->offsets || desc->offsets[0] != 0 || (desc->offsets[n] && !desc->cols)) {
-            set_error("row offsets: null array or first offset not 0");
-            return MBRWT_ERR_INVALID;
-        }
-        for (uint64_t r = 0; r < n; ++r) {
-            if (desc->offsets[r + 1] < desc->offsets[r]) {
-                set_error("row offsets not ascending");
-                return MBRWT_ERR_INVALID;
-            }
-            // (rows are sets: more labels than columns repeat one)
-            if (desc->offsets[r + 1] - desc->offsets[r] > m) {
-                set_error("a row of more labels than columns");
-                return MBRWT_ERR_INVALID;
-            }
-        }
+        if (const int rc = check_rows_desc(*desc)) return rc;
         Tree tree;
-        if (shape) {
-            if (const int rc = shape_tree(*shape, m, tree)) return rc;
-        } else {
-            std::vector<uint32_t> nc, fc, lc;
-            if (const int rc = basic_shape(m, arity, nc, fc, lc)) return rc;
-            const mbrwt_shape_desc sd{(uint32_t)nc.size(), nc.data(), fc.data(), lc.data()};
-            if (const int rc = shape_tree(sd, m, tree)) return rc;
-        }
+        if (const int rc = rows_shape_tree(shape, m, arity, tree)) return rc;
         return create_from_rows(*desc, tree, device, out);
     } catch (const std::bad_alloc &) {
         set_error("host allocation failed");
         return MBRWT_ERR_NOMEM;
     } catch (...) {
         set_error("unexpected exception in mbrwt_create_from_rows");
+        return MBRWT_ERR_INVALID;
+    }
+}
+
+int mbrwt_rows_node_counts(const mbrwt_rows_desc *desc, const mbrwt_shape_desc *shape, uint32_t arity, int device,
+                           uint64_t *counts) {
+    if (!desc || !counts) {
+        set_error("null rows description or output pointer");
+        return MBRWT_ERR_INVALID;
+    }
+    try {
+        const uint64_t n = desc->num_rows, m = desc->num_columns;
+        if (m == 0) {  // no leaf: whatever nodes the caller's shape names see no row
+            if (shape) std::fill(counts, counts + shape->num_nodes, 0);
+            return MBRWT_OK;
+        }
+        if (n && check_rows_desc(*desc)) return MBRWT_ERR_INVALID;
+        Tree tree;
+        if (const int rc = rows_shape_tree(shape, m, arity, tree)) return rc;
+        std::fill(counts, counts + tree.num_nodes, 0);
+        if (n == 0) return MBRWT_OK;
+        return rows_node_counts(*desc, tree, device, counts);
+    } catch (const std::bad_alloc &) {
+        set_error("host allocation failed");
+        return MBRWT_ERR_NOMEM;
+    } catch (...) {
+        set_error("unexpected exception in mbrwt_rows_node_counts");
+        return MBRWT_ERR_INVALID;
+    }
+}
+
+int mbrwt_tree_relax_shape(const mbrwt_shape_desc *shape, const uint64_t *counts, uint64_t max_arity,
+                           mbrwt_tree **out) {
+    if (!shape || !counts || !out) {
+        set_error("null shape, counts or output pointer");
+        return MBRWT_ERR_INVALID;
+    }
+    *out = nullptr;
+    try {
+        std::vector<uint32_t> nc, fc, lc;
+        if (const int rc = relax_shape(*shape, counts, max_arity, nc, fc, lc)) return rc;
+        uint64_t m = 0;
+        for (const uint32_t k : nc) m += k == 0;
+        return shape_only_tree(m, std::move(nc), std::move(fc), std::move(lc), out);
+    } catch (const std::bad_alloc &) {
+        set_error("host allocation failed");
+        return MBRWT_ERR_NOMEM;
+    } catch (...) {
+        set_error("unexpected exception in mbrwt_tree_relax_shape");
+        return MBRWT_ERR_INVALID;
+    }
+}
+
+int mbrwt_tree_shape_from_rows(const mbrwt_rows_desc *desc, int partitioner, uint32_t arity, uint64_t relax_max_arity,
+                               int device, mbrwt_tree **out) {
+    if (!desc || !out) {
+        set_error("null rows description or output pointer");
+        return MBRWT_ERR_INVALID;
+    }
+    *out = nullptr;
+    if (partitioner != MBRWT_PARTITIONER_BASIC && partitioner != MBRWT_PARTITIONER_GREEDY) {
+        set_error("partitioner must be MBRWT_PARTITIONER_BASIC or MBRWT_PARTITIONER_GREEDY");
+        return MBRWT_ERR_INVALID;
+    }
+    try {
+        const uint64_t n = desc->num_rows, m = desc->num_columns;
+        std::vector<uint32_t> nc, fc, lc;
+        if (n && m && check_rows_desc(*desc)) return MBRWT_ERR_INVALID;
+        if (partitioner == MBRWT_PARTITIONER_BASIC) {  // (reads no row: the labels are checked by the counts pass)
+            if (const int rc = basic_shape(m, arity, nc, fc, lc)) return rc;
+        } else {
+            if (const int rc = greedy_shape_from_rows(*desc, device, nc, fc, lc)) return rc;
+        }
+        if (relax_max_arity > 1 && nc.size() > 1) {
+            const mbrwt_shape_desc sd{(uint32_t)nc.size(), nc.data(), fc.data(), lc.data()};
+            std::vector<uint64_t> counts(nc.size(), 0);
+            if (const int rc = mbrwt_rows_node_counts(desc, &sd, 0, device, counts.data())) return rc;
+            std::vector<uint32_t> rn, rf, rl;
+            if (const int rc = relax_shape(sd, counts.data(), relax_max_arity, rn, rf, rl)) return rc;
+            nc.swap(rn);
+            fc.swap(rf);
+            lc.swap(rl);
+        }
+        return shape_only_tree(m, std::move(nc), std::move(fc), std::move(lc), out);
+    } catch (const std::bad_alloc &) {
+        set_error("host allocation failed");
+        return MBRWT_ERR_NOMEM;
+    } catch (...) {
+        set_error("unexpected exception in mbrwt_tree_shape_from_rows");
         return MBRWT_ERR_INVALID;
     }
 }

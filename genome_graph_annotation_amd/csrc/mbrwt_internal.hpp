@@ -489,6 +489,18 @@ const char *rows_limits_message();
 int basic_shape(uint64_t m, uint32_t arity, std::vector<uint32_t> &num_children, std::vector<uint32_t> &first_child,
                 std::vector<uint32_t> &leaf_column);
 int shape_tree(const mbrwt_shape_desc &shape, uint64_t num_columns, Tree &tree);
+// shapes from rows (build.hip), as BFS arrays:
+// binary_grouping_greedy over the row sample gathered from the CSR (the
+// unrelaxed shape; the sampled rows are checked), and BRWTOptimizer::relax of
+// a shape over per-node row counts (host only)
+int greedy_shape_from_rows(const mbrwt_rows_desc &desc, int device, std::vector<uint32_t> &num_children,
+                           std::vector<uint32_t> &first_child, std::vector<uint32_t> &leaf_column);
+int relax_shape(const mbrwt_shape_desc &shape, const uint64_t *counts, uint64_t max_arity,
+                std::vector<uint32_t> &num_children, std::vector<uint32_t> &first_child,
+                std::vector<uint32_t> &leaf_column);
+// an owned shape-only mbrwt_tree of BFS arrays (brwt_io.cpp)
+int shape_only_tree(uint64_t num_columns, std::vector<uint32_t> num_children, std::vector<uint32_t> first_child,
+                    std::vector<uint32_t> leaf_column, mbrwt_tree **out);
 // row records straight from CSR rows (rows_from.hip): the shape's device
 // table and the column -> pre-order index map once (rows_from_begin), then
 // per range [a, b) of rows the upload, the keys, the order check (a sort only
@@ -500,6 +512,16 @@ int rows_from_begin(const Tree &shape, hipStream_t s, RowsFrom **out);
 int rows_from_range(RowsFrom *rf, RowsBuild *rb, const uint64_t *offsets, const uint32_t *cols, uint64_t a, uint64_t b,
                     uint64_t *labels);
 void rows_from_end(RowsFrom *rf);
+// the first half of rows_from_range alone -- upload, keys, order check, sort --
+// for a caller that walks the rows itself (rows_counts.hip): *rows = the
+// range's label source, valid until the next load
+int rows_from_load(RowsFrom *rf, const uint64_t *offsets, const uint32_t *cols, uint64_t a, uint64_t b,
+                   LabelRows *rows);
+// per-node row counts (rows_counts.hip): adds, for every row
+// of the loaded range, 1 to d_counts[dnode] of every dnode of the shape table
+// with a label of the row below it (dnode 1 = the root: the non-empty rows)
+int rows_counts_range(const LabelRows &rows, uint64_t num_rows, uint32_t num_dnodes, unsigned long long *d_counts,
+                      hipStream_t s);
 // device bytes one range of `rows` rows and `labels` labels takes beside the
 // records (the sizing of the ranges, capi.cpp), and the most labels of a range
 uint64_t rows_from_range_bytes(uint64_t rows, uint64_t labels);

@@ -18,7 +18,9 @@
 //                emit_label_masks): measure, decide (first range), write, as
 //                for a node image.
 // The device holds the records plus ONE range's labels (6 bytes per label and
-// 4 per row; the sort's scratch only when a range needs it).
+// 4 per row; the sort's scratch only when a range needs it).  Everything
+// before the records is rows_from_load, which the per-node row counts
+// (rows_counts.hip) run too.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -218,8 +220,8 @@ static int sort_range(RowsFrom &rf, const uint64_t *offsets, uint64_t a, uint64_
     return MBRWT_OK;
 }
 
-int rows_from_range(RowsFrom *rf, RowsBuild *rb, const uint64_t *offsets, const uint32_t *cols, uint64_t a, uint64_t b,
-                    uint64_t *labels) {
+int rows_from_load(RowsFrom *rf, const uint64_t *offsets, const uint32_t *cols, uint64_t a, uint64_t b,
+                   LabelRows *rows) {
     const uint64_t nr = b - a, L = offsets[b] - offsets[a];
     if (L > kRowsFromMaxLabels) {
         set_error("row records from rows: more than 2^31 - 1 labels in one range of rows");
@@ -262,12 +264,18 @@ int rows_from_range(RowsFrom *rf, RowsBuild *rb, const uint64_t *offsets, const 
             return MBRWT_ERR_INVALID;
         }
     }
+    *rows = LabelRows{rf->d_shape, d_off, d_keys};
+    return MBRWT_OK;
+}
+
+int rows_from_range(RowsFrom *rf, RowsBuild *rb, const uint64_t *offsets, const uint32_t *cols, uint64_t a, uint64_t b,
+                    uint64_t *labels) {
     Ctx &range = rf->range;
-    range.tree.num_rows = nr;
-    range.tree.num_relations = L;
-    range.label_rows = LabelRows{rf->d_shape, d_off, d_keys};
-    if ((rc = rows_build_range(rb, range, a))) return rc;
-    *labels += L;
+    if (int rc = rows_from_load(rf, offsets, cols, a, b, &range.label_rows)) return rc;
+    range.tree.num_rows = b - a;
+    range.tree.num_relations = offsets[b] - offsets[a];
+    if (int rc = rows_build_range(rb, range, a)) return rc;
+    *labels += offsets[b] - offsets[a];
     return MBRWT_OK;
 }
 

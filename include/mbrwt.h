@@ -162,9 +162,9 @@ int mbrwt_create_relaxed(const mbrwt_tree_desc *desc, uint64_t max_arity, int de
  * memory less an 8 GiB reserve, at most 2^31 - 1 labels each;
  * MBRWT_BUILD_ROWS_RANGE fixes the size).  This is how a matrix too large for
  * mbrwt_create_from_columns (num_columns x ceil(num_rows / 64) words on the
- * host and the device) is built from data: the shape from a build of a row
- * sample (as binary_grouping_greedy samples 10^6 rows,
- * partitionings.cpp:148-196), the records from all rows, a .brwt through
+ * host and the device) is built from data: the shape from the same rows
+ * (mbrwt_tree_shape_from_rows: the greedy partitioner over its 10^6-row
+ * sample, relax over all rows), the records from all rows, a .brwt through
  * mbrwt_tree_export + mbrwt_tree_serialize.  The reference's annotators
  * produce such rows (annotate_row, RowCompressed).
  *
@@ -432,6 +432,46 @@ int mbrwt_tree_export(mbrwt_ctx *ctx, mbrwt_tree **out);
    arity outside 2..64 -> MBRWT_ERR_INVALID; num_columns == 0 gives the empty
    tree.  Host only, no GPU. */
 int mbrwt_tree_basic_shape(uint64_t num_columns, uint32_t arity, mbrwt_tree **out);
+
+/* ---- tree shapes straight from row-major data ------------
+ * The shape the reference's production build gives -- binary_grouping_greedy
+ * (partitionings.cpp:148-196) then BRWTOptimizer::relax (BRWT_builders.cpp:
+ * 166-297; `transform_anno --greedy`, `relax_brwt`) -- from the CSR of the
+ * rows alone: no dense column and no index column is built anywhere.
+ *
+ * mbrwt_rows_node_counts: counts[u] (num_nodes u64, host) = the rows of desc
+ * with a label below BFS node u of the shape (a leaf: its column's popcount;
+ * the root: the non-empty rows).  shape == NULL: mbrwt_tree_basic_shape(
+ * num_columns, arity).  One pass over all rows on the device, range by range
+ * as mbrwt_create_from_rows ranges (multiples of 360,360 rows sized from the
+ * free device memory, MBRWT_BUILD_ROWS_RANGE honoured); arguments, shape and
+ * rows are checked as there, with the same statuses.  Limits
+ * (MBRWT_ERR_UNSUPPORTED): more than 65,536 columns, a shape of height > 16,
+ * a row of more than 32,767 labels.  A one-column shape is allowed.
+ * num_rows == 0 or num_columns == 0: all-zero counts.
+ *
+ * mbrwt_tree_relax_shape: BRWTOptimizer::relax(max_arity) of `shape` given
+ * such counts -- a node's index column has counts[parent] bits of which
+ * counts[node] are set, and that is all relax's decisions read -- as an owned
+ * shape-only tree (vec_size 0, num_rows 0), renumbered breadth-first.
+ * max_arity <= 1: the shape unchanged.  Host only, no GPU.
+ *
+ * mbrwt_tree_shape_from_rows: partitioner MBRWT_PARTITIONER_BASIC (arity
+ * 2..64) or MBRWT_PARTITIONER_GREEDY (arity ignored; the similarities over
+ * the reference's row sample, gathered from the CSR), then, for
+ * relax_max_arity > 1, the counts over ALL rows and the relax above: the
+ * shape BRWTBottomUpBuilder::build + BRWTOptimizer::relax give on the dense
+ * matrix of these rows, ready for mbrwt_create_from_rows.  Another
+ * partitioner, or an arity outside 2..64 under BASIC -> MBRWT_ERR_INVALID.
+ * The greedy partitioner checks the sampled rows' columns, the counts pass
+ * those of every row; BASIC without relax reads no row.  The thread's
+ * MBRWT_BUILD_PARTITIONER is not read. */
+int mbrwt_rows_node_counts(const mbrwt_rows_desc *desc, const mbrwt_shape_desc *shape, uint32_t arity, int device,
+                           uint64_t *counts);
+int mbrwt_tree_relax_shape(const mbrwt_shape_desc *shape, const uint64_t *counts, uint64_t max_arity,
+                           mbrwt_tree **out);
+int mbrwt_tree_shape_from_rows(const mbrwt_rows_desc *desc, int partitioner, uint32_t arity,
+                               uint64_t relax_max_arity, int device, mbrwt_tree **out);
 const mbrwt_tree_desc *mbrwt_tree_get_desc(const mbrwt_tree *tree); /* valid until mbrwt_tree_free */
 void mbrwt_tree_free(mbrwt_tree *tree);
 int mbrwt_load(const uint8_t *bytes, uint64_t len, uint64_t *consumed, int device, mbrwt_ctx **out);

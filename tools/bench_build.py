@@ -28,7 +28,11 @@ ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--relax", type=int, default=0, help="then BRWTOptimizer::relax with this max arity")
 ap.add_argument("--from-rows", action="store_true",
                 help="the same matrix through from_rows (CSR rows) and from_columns(layout='rows'), reps alternating")
+ap.add_argument("--greedy", action="store_true",
+                help="binary_grouping_greedy instead of the basic partitioner; with --from-rows the shape comes from "
+                     "the rows (shape_from_rows) and its steps are timed one by one as well")
 a = ap.parse_args()
+PART = "greedy" if a.greedy else "basic"
 
 import oracle as O  # checker + CPU baseline only
 from genome_graph_annotation_amd import BRWTDevice
@@ -82,19 +86,21 @@ if a.from_rows:
     import torch
     torch.cuda.init()
     off, lab = csr_rows(cols, n)
-    BRWTDevice.from_rows(off[:1025], lab[: int(off[1024])], m, arity=a.arity).close()  # warm-up
-    BRWTDevice.from_columns(cols[: min(m, 16)], n, a.arity, layout="rows").close()
+    kw = dict(partitioner=PART, relax_max_arity=a.relax)
+    BRWTDevice.from_rows(off[:1025], lab[: int(off[1024])], m, arity=a.arity, **kw).close()  # warm-up
+    BRWTDevice.from_columns(cols[: min(m, 16)], n, a.arity, layout="rows", **kw).close()
     res = {"from_rows": {"s": [], "used": []}, "from_columns": {"s": [], "used": []}}
     for _ in range(a.reps):
         for name in ("from_rows", "from_columns"):
             with LowWater() as lw:
                 t0 = time.perf_counter()
-                built = (BRWTDevice.from_rows(off, lab, m, arity=a.arity) if name == "from_rows" else
-                         BRWTDevice.from_columns(cols, n, a.arity, layout="rows"))
+                built = (BRWTDevice.from_rows(off, lab, m, arity=a.arity, **kw) if name == "from_rows" else
+                         BRWTDevice.from_columns(cols, n, a.arity, layout="rows", **kw))
                 res[name]["s"].append(time.perf_counter() - t0)
             res[name]["used"].append(int(lw.before - lw.low))
             res[name]["image_bytes"] = int(built.device_bytes())
             res[name]["stats"] = built.rows_stats()
+            res[name]["shape"] = [built.export()[k].tolist() for k in ("num_children", "first_child", "leaf_column")]
             if name == "from_rows":
                 rows = np.random.default_rng(1).integers(0, n, 200_000).astype(np.uint64)
                 got = built.get_rows(rows)
@@ -103,28 +109,49 @@ if a.from_rows:
             built.close()
     same = (res["from_rows"]["image_bytes"] == res["from_columns"]["image_bytes"]
             and res["from_rows"]["stats"] == res["from_columns"]["stats"]
+            and res["from_rows"]["shape"] == res["from_columns"]["shape"]
             and all(np.array_equal(x, y) for x, y in zip(got, want)))
+    steps = {}
+    if a.greedy or a.relax:  # the steps of from_rows' shape, each on its own (their sum: one more full run)
+        from genome_graph_annotation_amd.brwt import node_counts_from_rows, relax_shape, shape_from_rows
+        steps = {"partition_s": [], "counts_s": [], "relax_s": [], "records_s": []}
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            plain = shape_from_rows(off, lab, m, PART, a.arity)
+            t1 = time.perf_counter()
+            counts = node_counts_from_rows(off, lab, m, shape=plain)
+            t2 = time.perf_counter()
+            shape = relax_shape(plain, counts, a.relax)
+            t3 = time.perf_counter()
+            BRWTDevice.from_rows(off, lab, m, shape=shape).close()
+            t4 = time.perf_counter()
+            for k, v in zip(steps, (t1 - t0, t2 - t1, t3 - t2, t4 - t3)):
+                steps[k].append(v)
+        steps = {k: {"median_s": float(np.median(v)), "runs_s": v} for k, v in steps.items()}
     print(json.dumps({
         "metric": "row-record build from host data to a queryable context: from_rows (CSR rows) against "
                   "from_columns(layout='rows') (dense columns), reps alternating in one process",
-        "config": {"rows": n, "columns": m, "density": a.density, "arity": a.arity, "relations": int(len(lab))},
+        "config": {"rows": n, "columns": m, "density": a.density, "arity": a.arity, "relations": int(len(lab)),
+                   "partitioner": PART, "relax_max_arity": a.relax, "nodes": len(res["from_rows"]["shape"][0])},
+        "from_rows_steps": steps,
         **{name: {"median_s": float(np.median(r["s"])), "runs_s": r["s"], "image_bytes": r["image_bytes"],
                   "device_low_water_used_bytes": int(max(r["used"])), "low_water_runs": r["used"]}
            for name, r in res.items()},
-        "parity": ("equal image bytes and rows_stats, identical get_rows on 200,000 rows" if same else "MISMATCH"),
+        "parity": ("equal shape, image bytes and rows_stats, identical get_rows on 200,000 rows" if same
+                   else "MISMATCH"),
     }))
     sys.exit(0 if same else 1)
 
-BRWTDevice.from_columns(cols[: min(m, 16)], n, a.arity).close()  # warm-up (HIP init, kernels)
+BRWTDevice.from_columns(cols[: min(m, 16)], n, a.arity, partitioner=PART).close()  # warm-up (HIP init, kernels)
 dev_s = []
 for _ in range(a.reps):
     t0 = time.perf_counter()
-    built = BRWTDevice.from_columns(cols, n, a.arity, relax_max_arity=a.relax)
+    built = BRWTDevice.from_columns(cols, n, a.arity, relax_max_arity=a.relax, partitioner=PART)
     dev_s.append(time.perf_counter() - t0)
     if _ + 1 < a.reps:
         built.close()
 t0 = time.perf_counter()
-t = O.OracleTree(O.lib().oracle_build_from_columns(O._p64(words), n, m, 0, a.arity, a.relax))
+t = O.OracleTree(O.lib().oracle_build_from_columns(O._p64(words), n, m, int(a.greedy), a.arity, a.relax))
 cpu_s = time.perf_counter() - t0
 ref = BRWTDevice.from_tree(t.export())
 rows = np.random.default_rng(1).integers(0, n, 200_000).astype(np.uint64)
@@ -132,7 +159,7 @@ o1, c1 = built.get_rows(rows)
 o2, c2 = t.get_rows(rows)
 same = built.device_bytes() == ref.device_bytes() and np.array_equal(o1, o2) and np.array_equal(c1, c2)
 print(json.dumps({
-    "metric": "BRWT build from columns (BRWTBottomUpBuilder::build, basic partitioner"
+    "metric": f"BRWT build from columns (BRWTBottomUpBuilder::build, {PART} partitioner"
               + (", then BRWTOptimizer::relax)" if a.relax else ")"),
     "config": {"rows": n, "columns": m, "density": a.density, "arity": a.arity, "relax_max_arity": a.relax,
                "nodes": int(built.num_nodes()),
