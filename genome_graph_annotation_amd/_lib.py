@@ -113,6 +113,16 @@ class RowsDesc(C.Structure):  # mbrwt_rows_desc: CSR rows (mbrwt_create_from_row
     ]
 
 
+class SparseColumnsDesc(C.Structure):  # mbrwt_sparse_columns_desc (mbrwt_create_from_sparse_columns)
+    _fields_ = [
+        ("num_rows", C.c_uint64),
+        ("num_columns", C.c_uint64),
+        ("offsets", u64p),
+        ("rows", u64p),
+        ("rows32", u32p),
+    ]
+
+
 class BinRelDesc(C.Structure):  # include/mbrwt_wt.h
     _fields_ = [
         ("num_rows", C.c_uint64),
@@ -147,6 +157,12 @@ SIGNATURES = {
     "mbrwt_tree_relax_shape": (C.c_int, [C.POINTER(ShapeDesc), u64p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "mbrwt_tree_shape_from_rows": (C.c_int, [C.POINTER(RowsDesc), C.c_int, C.c_uint32, C.c_uint64, C.c_int,
                                              C.POINTER(C.c_void_p)]),
+    "mbrwt_create_from_sparse_columns": (C.c_int, [C.POINTER(SparseColumnsDesc), C.POINTER(ShapeDesc), C.c_uint32,
+                                                   C.c_int, C.POINTER(C.c_void_p)]),
+    "mbrwt_sparse_columns_node_counts": (C.c_int, [C.POINTER(SparseColumnsDesc), C.POINTER(ShapeDesc), C.c_uint32,
+                                                   C.c_int, u64p]),
+    "mbrwt_tree_shape_from_sparse_columns": (C.c_int, [C.POINTER(SparseColumnsDesc), C.c_int, C.c_uint32, C.c_uint64,
+                                                       C.c_int, C.POINTER(C.c_void_p)]),
     "mbrwt_create_relaxed": (C.c_int, [C.POINTER(TreeDesc), C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]),
     "mbrwt_get_labels_batch": (C.c_int, [C.c_void_p, u64p, C.c_uint64, u64p, C.c_uint64, C.c_double, u64p, u32p,
                                          C.c_uint64, u64p]),

@@ -252,6 +252,54 @@ def shape_from_rows(offsets, cols, num_columns, partitioner="basic", arity=8, re
     return _shape_dict(h)
 
 
+def _sparse_columns_desc(col_offsets, col_rows, num_rows, num_columns):
+    """mbrwt_sparse_columns_desc and the arrays it points into: col_rows of
+    dtype uint32 go in as rows32, anything else as uint64 rows."""
+    off = np.ascontiguousarray(col_offsets, dtype=np.uint64)
+    if off.size != int(num_columns) + 1:
+        raise ValueError("col_offsets needs num_columns + 1 entries")
+    rows = np.asarray(col_rows)
+    narrow = rows.dtype == np.uint32
+    rows = np.ascontiguousarray(rows, dtype=np.uint32 if narrow else np.uint64)
+    if rows.size == 0:
+        rows = np.zeros(1, dtype=rows.dtype)
+    d = L.SparseColumnsDesc(int(num_rows), int(num_columns), _p(off, C.c_uint64),
+                            None if narrow else _p(rows, C.c_uint64), _p(rows, C.c_uint32) if narrow else None)
+    return d, (off, rows)
+
+
+def node_counts_from_sparse_columns(col_offsets, col_rows, num_rows, num_columns, shape=None, arity=8, device=0):
+    """node_counts_from_rows of the matrix given as sparse columns: column c
+    holds the rows col_rows[col_offsets[c]:col_offsets[c + 1]], strictly
+    ascending (mbrwt_sparse_columns_node_counts).  uint64 array."""
+    d, keep = _sparse_columns_desc(col_offsets, col_rows, num_rows, num_columns)
+    sd, keep_s = None, None
+    if shape is not None:
+        s, keep_s = _shape_desc(shape)
+        sd = C.byref(s)
+        nodes = len(keep_s[0])
+    else:
+        nodes = len(basic_shape(num_columns, arity)["num_children"])
+    counts = np.zeros(max(1, nodes), dtype=np.uint64)
+    L.check(L.lib().mbrwt_sparse_columns_node_counts(C.byref(d), sd, int(arity), device, _p(counts, C.c_uint64)),
+            "mbrwt_sparse_columns_node_counts")
+    del keep, keep_s
+    return counts[:nodes]
+
+
+def shape_from_sparse_columns(col_offsets, col_rows, num_rows, num_columns, partitioner="basic", arity=8,
+                              relax_max_arity=0, device=0):
+    """shape_from_rows of the matrix given as sparse columns
+    (mbrwt_tree_shape_from_sparse_columns): the same shape dict, node for node."""
+    d, keep = _sparse_columns_desc(col_offsets, col_rows, num_rows, num_columns)
+    part = L.PARTITIONERS[partitioner] if isinstance(partitioner, str) else int(partitioner)
+    h = C.c_void_p()
+    L.check(L.lib().mbrwt_tree_shape_from_sparse_columns(C.byref(d), part, int(arity), int(relax_max_arity), device,
+                                                         C.byref(h)), "mbrwt_tree_shape_from_sparse_columns")
+    del keep
+    return _shape_dict(h)
+
+
 @contextlib.contextmanager
 def build_layout(layout):
     """Device layout of the contexts created inside the block (None: the
@@ -390,6 +438,33 @@ class BRWTDevice:
             sd = C.byref(L.ShapeDesc(len(nc), _p(nc, C.c_uint32), _p(fc, C.c_uint32), _p(lc, C.c_uint32)))
         h = C.c_void_p()
         L.check(lib.mbrwt_create_from_rows(C.byref(d), sd, int(arity), device, C.byref(h)), "mbrwt_create_from_rows")
+        return cls(h)
+
+    @classmethod
+    def from_sparse_columns(cls, col_offsets, col_rows, num_rows, num_columns, arity=8, shape=None, device=0,
+                            partitioner="basic", relax_max_arity=0):
+        """Row records from sparse columns (mbrwt_create_from_sparse_columns):
+        column c holds the rows col_rows[col_offsets[c]:col_offsets[c + 1]],
+        strictly ascending (uint32 ids go in as they are, others as uint64).
+        `shape`, `arity`, `partitioner` and `relax_max_arity` as in from_rows
+        (the shape computed by shape_from_sparse_columns); the context equals
+        from_rows of the same matrix."""
+        if partitioner != "basic" or relax_max_arity:
+            if shape is not None:
+                raise ValueError("give a shape, or a partitioner / relax_max_arity to compute one: not both")
+            shape = shape_from_sparse_columns(col_offsets, col_rows, num_rows, num_columns, partitioner, arity,
+                                              relax_max_arity, device)
+            if len(shape["num_children"]) == 0:  # no column: the call below builds the empty context
+                shape = None
+        d, keep = _sparse_columns_desc(col_offsets, col_rows, num_rows, num_columns)
+        sd, keep_s = None, None
+        if shape is not None:
+            s, keep_s = _shape_desc(shape)
+            sd = C.byref(s)
+        h = C.c_void_p()
+        L.check(L.lib().mbrwt_create_from_sparse_columns(C.byref(d), sd, int(arity), device, C.byref(h)),
+                "mbrwt_create_from_sparse_columns")
+        del keep, keep_s
         return cls(h)
 
     @classmethod

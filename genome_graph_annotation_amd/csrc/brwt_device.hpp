@@ -214,6 +214,41 @@ class BRWTDevice : public BinaryMatrix {
         return build_from_rows(offsets, cols, num_columns, 2, td->num_nodes ? &shape : nullptr, device);
     }
 
+    // The same two from sparse columns (mbrwt_create_from_sparse_columns):
+    // column c = rows[offsets[c] .. offsets[c+1]), strictly ascending -- what
+    // ColumnCompressed::data()[c]->call_ones gives, the reference's own form
+    // before convert_to_BRWT.  The rows are transposed on the device.
+    static BRWTDevice build_from_sparse_columns(const std::vector<uint64_t> &offsets,
+                                                const std::vector<uint64_t> &rows, uint64_t num_rows,
+                                                uint32_t arity = 8, const mbrwt_shape_desc *shape = nullptr,
+                                                int device = 0) {
+        if (offsets.empty())
+            throw std::invalid_argument("build_from_sparse_columns: offsets needs num_columns + 1 entries");
+        const mbrwt_sparse_columns_desc d{num_rows, offsets.size() - 1, offsets.data(), rows.data(), nullptr};
+        BRWTDevice m(device);
+        mbrwt_ctx *c = nullptr;
+        check_status(mbrwt_create_from_sparse_columns(&d, shape, arity, device, &c),
+                     "mbrwt_create_from_sparse_columns");
+        m.ctx_.reset(c, Deleter());
+        return m;
+    }
+
+    static BRWTDevice build_from_sparse_columns_greedy(const std::vector<uint64_t> &offsets,
+                                                       const std::vector<uint64_t> &rows, uint64_t num_rows,
+                                                       uint64_t relax_max_arity = 0, int device = 0) {
+        if (offsets.empty())
+            throw std::invalid_argument("build_from_sparse_columns_greedy: offsets needs num_columns + 1 entries");
+        const mbrwt_sparse_columns_desc d{num_rows, offsets.size() - 1, offsets.data(), rows.data(), nullptr};
+        mbrwt_tree *t = nullptr;
+        check_status(mbrwt_tree_shape_from_sparse_columns(&d, MBRWT_PARTITIONER_GREEDY, 2, relax_max_arity, device,
+                                                          &t),
+                     "mbrwt_tree_shape_from_sparse_columns");
+        std::unique_ptr<mbrwt_tree, void (*)(mbrwt_tree *)> owned(t, mbrwt_tree_free);
+        const mbrwt_tree_desc *td = mbrwt_tree_get_desc(t);
+        const mbrwt_shape_desc shape{td->num_nodes, td->num_children, td->first_child, td->leaf_column};
+        return build_from_sparse_columns(offsets, rows, num_rows, 2, td->num_nodes ? &shape : nullptr, device);
+    }
+
     // a query handle over the same device image (mbrwt_ctx_clone): one per
     // server worker thread, so their get_rows calls do not serialise on a
     // shared workspace (the reference shares its annotator by reference

@@ -958,6 +958,151 @@ int relax_shape(const mbrwt_shape_desc &shape, const uint64_t *counts, uint64_t 
     return MBRWT_OK;
 }
 
+// The greedy shape from data alone: a front end fills
+// the m zeroed sample columns (SW words each) from its form of the data --
+// CSR rows (greedy_shape_from_rows) or sparse columns
+// (greedy_shape_from_sparse_columns) -- and greedy_levels partitions level
+// after level over them.
+namespace {
+
+struct ShapeScope {  // the stream and the device allocations of one shape call
+    hipStream_t s = nullptr;
+    std::vector<void *> allocs;
+    void *alloc(size_t bytes) {
+        void *p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
+        allocs.push_back(p);
+        return p;
+    }
+    ~ShapeScope() {
+        if (s) (void)hipStreamSynchronize(s);
+        for (void *p : allocs) (void)hipFree(p);
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+
+int shape_scope_open(ShapeScope &sc, int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        set_error("no HIP device available");
+        return MBRWT_ERR_DEVICE;
+    }
+    if (device < 0 || device >= ndev) {
+        set_error("device index out of range");
+        return MBRWT_ERR_INVALID;
+    }
+    MBRWT_HIP(hipSetDevice(device));
+    MBRWT_HIP(hipStreamCreateWithFlags(&sc.s, hipStreamNonBlocking));
+    return MBRWT_OK;
+}
+
+// the m zeroed sample columns of SW words
+int sample_columns(ShapeScope &sc, uint64_t m, uint64_t SW, uint64_t **d_samp) {
+    *d_samp = reinterpret_cast<uint64_t *>(sc.alloc(m * SW * sizeof(uint64_t)));
+    if (!*d_samp) return hip_fail(hipErrorOutOfMemory, "builder allocation");
+    MBRWT_HIP(hipMemsetAsync(*d_samp, 0, std::max<uint64_t>(m * SW * sizeof(uint64_t), 8), sc.s));
+    return MBRWT_OK;
+}
+
+// bit `slot` of sample column c for every slot of the column's list: one
+// workgroup per column, so a column's words are touched by that workgroup
+// alone (its lanes meet in a word: a workgroup-local atomic OR)
+__global__ __launch_bounds__(256) void k_sample_scatter_cols(const uint64_t *__restrict__ soff, uint32_t c0,
+                                                             uint32_t nc, const uint32_t *__restrict__ slots,
+                                                             uint64_t SW, unsigned long long *samp) {
+    for (uint32_t j = blockIdx.x; j < nc; j += gridDim.x) {
+        const uint64_t a = gld(soff + j), b = gld(soff + j + 1);
+        unsigned long long *col = samp + (uint64_t)(c0 + j) * SW;
+        for (uint64_t p = a + threadIdx.x; p < b; p += 256) {
+            const uint32_t k = gld(slots + p);
+            if ((k >> 6) < SW) atomicOr(col + (k >> 6), 1ull << (k & 63));  // (the host made the slots)
+        }
+    }
+}
+
+int greedy_levels(ShapeScope &sc, uint64_t *d_samp, uint64_t m, uint64_t SW, const char *what,
+                  std::vector<uint32_t> &num_children, std::vector<uint32_t> &first_child,
+                  std::vector<uint32_t> &leaf_column);
+
+}  // namespace
+
+int greedy_shape_from_sparse_columns(const ColsView &v, int device, std::vector<uint32_t> &num_children,
+                                     std::vector<uint32_t> &first_child, std::vector<uint32_t> &leaf_column) {
+    num_children.clear();
+    first_child.clear();
+    leaf_column.clear();
+    const uint64_t n = v.num_rows, m = v.num_columns;
+    if (m > 0xFFFFFFFFull) {
+        set_error("num_columns >= 2^32 is not supported by this build");
+        return MBRWT_ERR_UNSUPPORTED;
+    }
+    if (m == 0) return MBRWT_OK;
+    if (m == 1) {  // the single leaf
+        num_children.assign(1, 0);
+        first_child.assign(1, 0);
+        leaf_column.assign(1, 0);
+        return MBRWT_OK;
+    }
+    std::vector<uint64_t> sample;
+    const bool sample_all = n <= 1000000;
+    if (!sample_all) sample = greedy_sample_rows(n);
+    const uint64_t ns = sample_all ? n : sample.size(), SW = (ns + 63) / 64;
+    ShapeScope sc;
+    if (const int rc = shape_scope_open(sc, device)) return rc;
+    uint64_t *d_samp = nullptr;
+    if (const int rc = sample_columns(sc, m, SW, &d_samp)) return rc;
+    // batches of columns of at most kBatch slots (one column: at most 10^6):
+    // their slot lists gathered on up to 16 host threads, uploaded, scattered
+    constexpr uint64_t kBatch = 1ull << 26;
+    uint32_t *d_slots = nullptr;
+    uint64_t *d_soff = nullptr;
+    uint64_t slots_cap = 0, soff_cap = 0;
+    for (uint64_t c0 = 0, c1; n && c0 < m; c0 = c1) {
+        uint64_t bound = 0;  // (a column gives at most min(its ids, the sample) slots)
+        for (c1 = c0; c1 < m; ++c1) {
+            const uint64_t len = std::min(v.offsets[c1 + 1] - v.offsets[c1], ns);
+            if (c1 > c0 && bound + len > kBatch) break;
+            bound += len;
+        }
+        const uint64_t nc = c1 - c0;
+        std::vector<std::vector<uint32_t>> part(nc);
+        std::vector<uint8_t> ok(nc, 1);
+        const unsigned T = cols_threads(v.offsets[c1] - v.offsets[c0]);
+        cols_parallel(T, [&](unsigned t) {
+            for (uint64_t j = t; j < nc; j += T)
+                ok[j] = cols_sample_slots(v, c0 + j, sample_all ? nullptr : &sample, part[j]);
+        });
+        std::vector<uint64_t> soff(nc + 1, 0);
+        for (uint64_t j = 0; j < nc; ++j) {
+            if (!ok[j]) {
+                set_error("sparse columns: a row id >= num_rows, or a column's row ids do not ascend strictly");
+                return MBRWT_ERR_INVALID;
+            }
+            soff[j + 1] = soff[j] + part[j].size();
+        }
+        if (!soff[nc]) continue;
+        std::vector<uint32_t> slots(soff[nc]);
+        for (uint64_t j = 0; j < nc; ++j) std::copy(part[j].begin(), part[j].end(), slots.begin() + soff[j]);
+        if (slots.size() > slots_cap) {
+            d_slots = reinterpret_cast<uint32_t *>(sc.alloc(slots.size() * 4));
+            slots_cap = slots.size();
+        }
+        if (nc + 1 > soff_cap) {
+            d_soff = reinterpret_cast<uint64_t *>(sc.alloc((nc + 1) * 8));
+            soff_cap = nc + 1;
+        }
+        if (!d_slots || !d_soff) return hip_fail(hipErrorOutOfMemory, "builder allocation");
+        MBRWT_HIP(hipMemcpyAsync(d_soff, soff.data(), (nc + 1) * 8, hipMemcpyHostToDevice, sc.s));
+        MBRWT_HIP(hipMemcpyAsync(d_slots, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, sc.s));
+        hipLaunchKernelGGL(k_sample_scatter_cols, dim3((unsigned)std::min<uint64_t>(nc, 65536)), dim3(256), 0, sc.s,
+                           d_soff, (uint32_t)c0, (uint32_t)nc, d_slots, SW,
+                           reinterpret_cast<unsigned long long *>(d_samp));
+        MBRWT_HIP(hipGetLastError());
+        MBRWT_HIP(hipStreamSynchronize(sc.s));  // (the batch's host tables go out of scope)
+    }
+    return greedy_levels(sc, d_samp, m, SW, "sparse columns", num_children, first_child, leaf_column);
+}
+
 int greedy_shape_from_rows(const mbrwt_rows_desc &desc, int device, std::vector<uint32_t> &num_children,
                            std::vector<uint32_t> &first_child, std::vector<uint32_t> &leaf_column) {
     num_children.clear();
@@ -1003,46 +1148,36 @@ int greedy_shape_from_rows(const mbrwt_rows_desc &desc, int device, std::vector<
         leaf_column.assign(1, 0);
         return MBRWT_OK;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_error("no HIP device available");
-        return MBRWT_ERR_DEVICE;
-    }
-    if (device < 0 || device >= ndev) {
-        set_error("device index out of range");
-        return MBRWT_ERR_INVALID;
-    }
-    MBRWT_HIP(hipSetDevice(device));
-    struct Scope {
-        hipStream_t s = nullptr;
-        std::vector<void *> allocs;
-        void *alloc(size_t bytes) {
-            void *p = nullptr;
-            if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
-            allocs.push_back(p);
-            return p;
-        }
-        ~Scope() {
-            if (s) (void)hipStreamSynchronize(s);
-            for (void *p : allocs) (void)hipFree(p);
-            if (s) (void)hipStreamDestroy(s);
-        }
-    } sc;
-    MBRWT_HIP(hipStreamCreateWithFlags(&sc.s, hipStreamNonBlocking));
+    ShapeScope sc;
+    if (const int rc = shape_scope_open(sc, device)) return rc;
     hipStream_t s = sc.s;
     uint64_t *d_off = reinterpret_cast<uint64_t *>(sc.alloc((ns + 1) * sizeof(uint64_t)));
     uint32_t *d_scols = reinterpret_cast<uint32_t *>(sc.alloc(scols.size() * sizeof(uint32_t)));
-    uint64_t *d_samp = reinterpret_cast<uint64_t *>(sc.alloc(m * SW * sizeof(uint64_t)));
-    if (!d_off || !d_scols || !d_samp) return hip_fail(hipErrorOutOfMemory, "builder allocation");
+    if (!d_off || !d_scols) return hip_fail(hipErrorOutOfMemory, "builder allocation");
+    uint64_t *d_samp = nullptr;
+    if (const int rc = sample_columns(sc, m, SW, &d_samp)) return rc;
     MBRWT_HIP(hipMemcpyAsync(d_off, soff.data(), (ns + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     if (!scols.empty())
         MBRWT_HIP(hipMemcpyAsync(d_scols, scols.data(), scols.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    MBRWT_HIP(hipMemsetAsync(d_samp, 0, std::max<uint64_t>(m * SW * sizeof(uint64_t), 8), s));
     if (ns) {
         hipLaunchKernelGGL(k_sample_scatter, dim3(grid256(ns)), dim3(256), 0, s, d_off, ns, d_scols, m, SW,
                            reinterpret_cast<unsigned long long *>(d_samp));
         MBRWT_HIP(hipGetLastError());
     }
+    // (the host tables are pageable and die with this frame: the copies have read them)
+    MBRWT_HIP(hipStreamSynchronize(s));
+    return greedy_levels(sc, d_samp, m, SW, "rows", num_children, first_child, leaf_column);
+}
+
+namespace {
+
+// binary_grouping_greedy over the sample columns: level after level the
+// products on the device, the matching on the host, the parents' sample
+// columns the OR of their children's
+int greedy_levels(ShapeScope &sc, uint64_t *d_samp, uint64_t m, uint64_t SW, const char *what,
+                  std::vector<uint32_t> &num_children, std::vector<uint32_t> &first_child,
+                  std::vector<uint32_t> &leaf_column) {
+    hipStream_t s = sc.s;
     std::vector<BNode> nodes(m);
     std::vector<uint32_t> level(m);
     for (uint32_t j = 0; j < m; ++j) {
@@ -1102,10 +1237,12 @@ int greedy_shape_from_rows(const mbrwt_rows_desc &desc, int device, std::vector<
         level.swap(next);
     }
     if (const char *e = std::getenv("MBRWT_BUILD_TIMING"); e && e[0] == '1')
-        std::fprintf(stderr, "[mbrwt shape from rows] greedy: similarities %.1f ms, sort + matching %.1f ms\n", sim_ms,
-                     sort_ms);
+        std::fprintf(stderr, "[mbrwt shape from %s] greedy: similarities %.1f ms, sort + matching %.1f ms\n", what,
+                     sim_ms, sort_ms);
     bfs_shape(nodes, level[0], num_children, first_child, leaf_column);
     return MBRWT_OK;
 }
+
+}  // namespace
 
 }  // namespace mbrwt

@@ -372,24 +372,19 @@ struct RowsFromEnd {
 // `off` whose labels fit the free device memory less the reserve and
 // `pending` (the bytes the build will still allocate); a fixed range size
 // (MBRWT_BUILD_ROWS_RANGE) is taken as it is
-static uint64_t cut_rows_range(const uint64_t *off, uint64_t n, uint64_t a, uint64_t R, uint64_t pending) {
-    uint64_t b = std::min(n, a + R);
-    if (build_tuning().rows_range != 0) return b;
+static double range_budget(uint64_t pending) {
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
     const double left = (double)free_b - 8.0 * (1ull << 30) - (double)pending;
-    const double budget = std::max(left, (double)free_b / 8) / 1.2;
-    auto fits = [&](uint64_t e) {
+    return std::max(left, (double)free_b / 8) / 1.2;
+}
+static uint64_t cut_rows_range(const uint64_t *off, uint64_t n, uint64_t a, uint64_t R, uint64_t pending) {
+    if (build_tuning().rows_range != 0) return std::min(n, a + R);
+    const double budget = range_budget(pending);
+    return cut_range_fit(n, a, R, kRowsAlign, [&](uint64_t e) {
         const uint64_t L = off[e] - off[a];
         return L <= kRowsFromMaxLabels && (double)rows_from_range_bytes(e - a, L) <= budget;
-    };
-    if (fits(b)) return b;
-    uint64_t lo = 1, hi = (b - a + kRowsAlign - 1) / kRowsAlign;  // lo: taken whatever it costs
-    while (lo + 1 < hi) {
-        const uint64_t mid = (lo + hi) / 2;
-        (fits(a + mid * kRowsAlign) ? lo : hi) = mid;
-    }
-    return std::min(n, a + lo * kRowsAlign);
+    });
 }
 
 static int create_from_rows(const mbrwt_rows_desc &desc, const Tree &shape, int device, mbrwt_ctx **out) {
@@ -422,14 +417,15 @@ static int create_from_rows(const mbrwt_rows_desc &desc, const Tree &shape, int 
         kNoLayoutHook);
 }
 
-// Per-node row counts of CSR rows under a tree shape (rows_counts.hip;
-// DESIGN.md §11c): the ranges, the upload, the keys and the sort of
-// create_from_rows without any record, so a range takes the memory the
-// records would; the counts accumulate on the device across the ranges and
-// come back once, dnode u + 1 of the shape table being BFS node u.
-static int rows_node_counts(const mbrwt_rows_desc &desc, const Tree &shape, int device, uint64_t *counts) {
-    const uint64_t n = desc.num_rows;
-    const uint64_t *off = desc.offsets;
+// Per-node row counts under a tree shape (rows_counts.hip):
+// the ranges and the loader of the build without any record, so a range takes
+// the memory the records would; the counts accumulate on the device across
+// the ranges and come back once, dnode u + 1 of the shape table being BFS
+// node u.  The frame both sources share: the walk's limits, pre() (the
+// source's own host checks), the device, the stream, the loader and the
+// counters; ranges(rf, d_counts, stream) loads every range and counts it.
+template <class Pre, class Ranges>
+static int node_counts_over(const Tree &shape, int device, uint64_t *counts, Pre pre, Ranges ranges) {
     const size_t D = shape.nodes.size();
     // the walk's limits (rows_emit.hpp emit_label_masks): internal levels on a path
     std::vector<uint32_t> level(D, 0);
@@ -443,11 +439,7 @@ static int rows_node_counts(const mbrwt_rows_desc &desc, const Tree &shape, int 
         }
         for (uint32_t c = 0; c < dn.arity; ++c) level[dn.first_child + c] = level[v] + 1;
     }
-    for (uint64_t r = 0; r < n; ++r)
-        if (off[r + 1] - off[r] > 0x7FFFu) {
-            set_error("row record deeper than the build walker supports, or a row of more than 32,767 labels");
-            return MBRWT_ERR_UNSUPPORTED;
-        }
+    if (int rc = pre()) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         set_error("no HIP device available");
@@ -472,19 +464,119 @@ static int rows_node_counts(const mbrwt_rows_desc &desc, const Tree &shape, int 
     if (int rc = rows_from_begin(shape, sc.s, &sc.rf)) return rc;
     MBRWT_HIP(hipMalloc(&sc.d_counts, D * sizeof(uint64_t)));
     MBRWT_HIP(hipMemsetAsync(sc.d_counts, 0, D * sizeof(uint64_t), sc.s));
-    for (uint64_t a = 0, b = 0; a < n; a = b) {
-        b = cut_rows_range(off, n, a, rows_range_rows(), 0);
-        LabelRows rows;
-        if (int rc = rows_from_load(sc.rf, off, desc.cols, a, b, &rows)) return rc;
-        if (int rc = rows_counts_range(rows, b - a, (uint32_t)D, sc.d_counts, sc.s)) return rc;
-        // (the next load overwrites the range's buffers)
-        MBRWT_HIP(hipStreamSynchronize(sc.s));
-    }
+    if (int rc = ranges(sc.rf, sc.d_counts, sc.s)) return rc;
     std::vector<unsigned long long> h(D);
     MBRWT_HIP(hipMemcpyAsync(h.data(), sc.d_counts, D * sizeof(uint64_t), hipMemcpyDeviceToHost, sc.s));
     MBRWT_HIP(hipStreamSynchronize(sc.s));
     for (size_t u = 0; u + 1 < D; ++u) counts[u] = h[u + 1];
     return MBRWT_OK;
+}
+
+static int rows_node_counts(const mbrwt_rows_desc &desc, const Tree &shape, int device, uint64_t *counts) {
+    const uint64_t n = desc.num_rows;
+    const uint64_t *off = desc.offsets;
+    const uint32_t D = (uint32_t)shape.nodes.size();
+    return node_counts_over(
+        shape, device, counts,
+        [&]() {
+            for (uint64_t r = 0; r < n; ++r)
+                if (off[r + 1] - off[r] > 0x7FFFu) {
+                    set_error("row record deeper than the build walker supports, or a row of more than 32,767 labels");
+                    return (int)MBRWT_ERR_UNSUPPORTED;
+                }
+            return (int)MBRWT_OK;
+        },
+        [&](RowsFrom *rf, unsigned long long *d_counts, hipStream_t s) {
+            for (uint64_t a = 0, b = 0; a < n; a = b) {
+                b = cut_rows_range(off, n, a, rows_range_rows(), 0);
+                LabelRows rows;
+                if (int rc = rows_from_load(rf, off, desc.cols, a, b, &rows)) return rc;
+                if (int rc = rows_counts_range(rows, b - a, D, d_counts, s)) return rc;
+                // (the next load overwrites the range's buffers)
+                MBRWT_HIP(hipStreamSynchronize(s));
+            }
+            return (int)MBRWT_OK;
+        });
+}
+
+// The same two from sparse columns (rows_from_cols.hip): one
+// cursor per column walks the ranges; a range is cut from the cursors
+// (cols_host.hpp cut_cols_range: the labels of a candidate range by bisection
+// from every cursor) and its slices end where the next range's begin.
+static ColsView cols_view(const mbrwt_sparse_columns_desc &d) {
+    ColsView v;
+    v.num_rows = d.num_rows;
+    v.num_columns = d.num_columns;
+    v.offsets = d.offsets;
+    v.rows = d.rows;
+    v.rows32 = d.rows32;
+    return v;
+}
+struct ColsRanges {
+    ColsView v;
+    std::vector<uint64_t> cur, ends;
+    explicit ColsRanges(const mbrwt_sparse_columns_desc &d) : v(cols_view(d)), cur(d.offsets, d.offsets + d.num_columns) {}
+    // the range after a: [a, b), its slices [cur, ends)
+    uint64_t cut(uint64_t a, uint64_t R, uint64_t pending) {
+        const bool fixed = build_tuning().rows_range != 0;
+        const uint64_t b = cut_cols_range(v.num_rows, v.num_columns, a, R, kRowsAlign, fixed,
+                                          fixed ? 0.0 : range_budget(pending),
+                                          [&](uint64_t e) { return cols_cut_slices(v, cur, e, nullptr); });
+        cols_cut_slices(v, cur, b, &ends);
+        return b;
+    }
+    void advance() { cur.swap(ends); }
+};
+
+static int create_from_sparse_columns(const mbrwt_sparse_columns_desc &desc, const Tree &shape, int device,
+                                      mbrwt_ctx **out) {
+    const uint64_t n = desc.num_rows;
+    return create_common(
+        device, out,
+        [&](Ctx &c) {
+            c.tree = shape;
+            c.tree.num_rows = n;
+            RowsFrom *rfp = nullptr;
+            if (int rc = rows_from_begin(c.tree, c.stream, &rfp)) return rc;
+            std::unique_ptr<RowsFrom, RowsFromEnd> rf(rfp);
+            RowsBuildPtr rb(rows_build_begin(c, n, kRowsAlign, false));
+            if (!rb) return (int)MBRWT_ERR_NOMEM;
+            const bool fixed = build_tuning().rows_range != 0;
+            ColsRanges rg(desc);
+            for (uint64_t a = 0, b = 0; a < n; a = b) {
+                b = rg.cut(a, fixed || a ? rows_range_rows() : std::min(rows_range_rows(), kRowsFirstRange),
+                           fixed ? 0 : rows_build_pending_bytes(rb.get(), n - a));
+                if (int rc = cols_from_range(rf.get(), rb.get(), rg.v, rg.cur, rg.ends, a, b, &c.tree.num_relations))
+                    return rc;  // (rb frees the build)
+                rg.advance();
+            }
+            rf.reset();
+            if (int rc = rows_build_finish(rb.release())) return rc;
+            c.nodes_freed = true;
+            return (int)MBRWT_OK;
+        },
+        kNoLayoutHook);
+}
+
+static int sparse_columns_node_counts(const mbrwt_sparse_columns_desc &desc, const Tree &shape, int device,
+                                      uint64_t *counts) {
+    const uint64_t n = desc.num_rows;
+    const uint32_t D = (uint32_t)shape.nodes.size();
+    return node_counts_over(
+        shape, device, counts, []() { return (int)MBRWT_OK; },
+        [&](RowsFrom *rf, unsigned long long *d_counts, hipStream_t s) {
+            ColsRanges rg(desc);
+            for (uint64_t a = 0, b = 0; a < n; a = b) {
+                b = rg.cut(a, rows_range_rows(), 0);
+                LabelRows rows;
+                uint64_t L = 0;
+                if (int rc = cols_from_load(rf, rg.v, rg.cur, rg.ends, a, b, &rows, &L)) return rc;
+                if (int rc = rows_counts_range(rows, b - a, D, d_counts, s)) return rc;
+                MBRWT_HIP(hipStreamSynchronize(s));
+                rg.advance();
+            }
+            return (int)MBRWT_OK;
+        });
 }
 
 // Layouts ROWS and AUTO over many rows build ranged: beyond kAutoRangedRows
@@ -566,6 +658,40 @@ static int check_rows_desc(const mbrwt_rows_desc &d) {
             set_error("a row of more labels than columns");
             return MBRWT_ERR_INVALID;
         }
+    }
+    return MBRWT_OK;
+}
+
+// the same for sparse columns of num_rows > 0 rows and num_columns > 0
+// columns; the ids themselves are checked on the device (rows_from_cols.hip)
+static int check_sparse_columns_desc(const mbrwt_sparse_columns_desc &d) {
+    const uint64_t n = d.num_rows, m = d.num_columns;
+    if (!d.offsets || d.offsets[0] != 0) {
+        set_error("column offsets: null array or first offset not 0");
+        return MBRWT_ERR_INVALID;
+    }
+    for (uint64_t c = 0; c < m; ++c) {
+        if (d.offsets[c + 1] < d.offsets[c]) {
+            set_error("column offsets not ascending");
+            return MBRWT_ERR_INVALID;
+        }
+        // (columns are sets: more ids than rows repeat one)
+        if (d.offsets[c + 1] - d.offsets[c] > n) {
+            set_error("a column of more row ids than rows");
+            return MBRWT_ERR_INVALID;
+        }
+    }
+    if (d.rows && d.rows32) {
+        set_error("sparse columns: both rows and rows32 given");
+        return MBRWT_ERR_INVALID;
+    }
+    if (d.offsets[m] && !d.rows && !d.rows32) {
+        set_error("sparse columns: neither rows nor rows32 given");
+        return MBRWT_ERR_INVALID;
+    }
+    if (d.rows32 && n > (1ull << 32)) {
+        set_error("sparse columns: rows32 with num_rows > 2^32");
+        return MBRWT_ERR_INVALID;
     }
     return MBRWT_OK;
 }
@@ -812,6 +938,105 @@ int mbrwt_tree_shape_from_rows(const mbrwt_rows_desc *desc, int partitioner, uin
         return MBRWT_ERR_NOMEM;
     } catch (...) {
         set_error("unexpected exception in mbrwt_tree_shape_from_rows");
+        return MBRWT_ERR_INVALID;
+    }
+}
+
+int mbrwt_create_from_sparse_columns(const mbrwt_sparse_columns_desc *desc, const mbrwt_shape_desc *shape,
+                                     uint32_t arity, int device, mbrwt_ctx **out) {
+    if (!desc || !out) {
+        set_error("null sparse columns description or output pointer");
+        return MBRWT_ERR_INVALID;
+    }
+    *out = nullptr;
+    try {
+        const int layout = resolve_layout();
+        if (layout == LAYOUT_NODES || layout == LAYOUT_BOTH) {
+            set_error("mbrwt_create_from_sparse_columns builds row records only: layout AUTO or ROWS");
+            return MBRWT_ERR_UNSUPPORTED;
+        }
+        const uint64_t n = desc->num_rows, m = desc->num_columns;
+        if (n == 0 || m == 0) {  // the context of the same empty matrix from its (empty) dense columns
+            std::vector<const uint64_t *> none(m, nullptr);
+            const mbrwt_columns_desc cd{n, m, none.data(), shape ? 2u : arity};
+            return mbrwt_create_from_columns(&cd, device, out);
+        }
+        if (const int rc = check_sparse_columns_desc(*desc)) return rc;
+        Tree tree;
+        if (const int rc = rows_shape_tree(shape, m, arity, tree)) return rc;
+        return create_from_sparse_columns(*desc, tree, device, out);
+    } catch (const std::bad_alloc &) {
+        set_error("host allocation failed");
+        return MBRWT_ERR_NOMEM;
+    } catch (...) {
+        set_error("unexpected exception in mbrwt_create_from_sparse_columns");
+        return MBRWT_ERR_INVALID;
+    }
+}
+
+int mbrwt_sparse_columns_node_counts(const mbrwt_sparse_columns_desc *desc, const mbrwt_shape_desc *shape,
+                                     uint32_t arity, int device, uint64_t *counts) {
+    if (!desc || !counts) {
+        set_error("null sparse columns description or output pointer");
+        return MBRWT_ERR_INVALID;
+    }
+    try {
+        const uint64_t n = desc->num_rows, m = desc->num_columns;
+        if (m == 0) {  // no leaf: whatever nodes the caller's shape names see no row
+            if (shape) std::fill(counts, counts + shape->num_nodes, 0);
+            return MBRWT_OK;
+        }
+        if (n && check_sparse_columns_desc(*desc)) return MBRWT_ERR_INVALID;
+        Tree tree;
+        if (const int rc = rows_shape_tree(shape, m, arity, tree)) return rc;
+        std::fill(counts, counts + tree.num_nodes, 0);
+        if (n == 0) return MBRWT_OK;
+        return sparse_columns_node_counts(*desc, tree, device, counts);
+    } catch (const std::bad_alloc &) {
+        set_error("host allocation failed");
+        return MBRWT_ERR_NOMEM;
+    } catch (...) {
+        set_error("unexpected exception in mbrwt_sparse_columns_node_counts");
+        return MBRWT_ERR_INVALID;
+    }
+}
+
+int mbrwt_tree_shape_from_sparse_columns(const mbrwt_sparse_columns_desc *desc, int partitioner, uint32_t arity,
+                                         uint64_t relax_max_arity, int device, mbrwt_tree **out) {
+    if (!desc || !out) {
+        set_error("null sparse columns description or output pointer");
+        return MBRWT_ERR_INVALID;
+    }
+    *out = nullptr;
+    if (partitioner != MBRWT_PARTITIONER_BASIC && partitioner != MBRWT_PARTITIONER_GREEDY) {
+        set_error("partitioner must be MBRWT_PARTITIONER_BASIC or MBRWT_PARTITIONER_GREEDY");
+        return MBRWT_ERR_INVALID;
+    }
+    try {
+        const uint64_t n = desc->num_rows, m = desc->num_columns;
+        std::vector<uint32_t> nc, fc, lc;
+        if (n && m && check_sparse_columns_desc(*desc)) return MBRWT_ERR_INVALID;
+        if (partitioner == MBRWT_PARTITIONER_BASIC) {  // (reads no id: the counts pass checks them)
+            if (const int rc = basic_shape(m, arity, nc, fc, lc)) return rc;
+        } else {
+            if (const int rc = greedy_shape_from_sparse_columns(cols_view(*desc), device, nc, fc, lc)) return rc;
+        }
+        if (relax_max_arity > 1 && nc.size() > 1) {
+            const mbrwt_shape_desc sd{(uint32_t)nc.size(), nc.data(), fc.data(), lc.data()};
+            std::vector<uint64_t> counts(nc.size(), 0);
+            if (const int rc = mbrwt_sparse_columns_node_counts(desc, &sd, 0, device, counts.data())) return rc;
+            std::vector<uint32_t> rn, rf, rl;
+            if (const int rc = relax_shape(sd, counts.data(), relax_max_arity, rn, rf, rl)) return rc;
+            nc.swap(rn);
+            fc.swap(rf);
+            lc.swap(rl);
+        }
+        return shape_only_tree(m, std::move(nc), std::move(fc), std::move(lc), out);
+    } catch (const std::bad_alloc &) {
+        set_error("host allocation failed");
+        return MBRWT_ERR_NOMEM;
+    } catch (...) {
+        set_error("unexpected exception in mbrwt_tree_shape_from_sparse_columns");
         return MBRWT_ERR_INVALID;
     }
 }

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../../include/mbrwt.h"
+#include "cols_host.hpp"
 
 namespace mbrwt {
 
@@ -507,7 +508,24 @@ int shape_only_tree(uint64_t num_columns, std::vector<uint32_t> num_children, st
 // where a row is not ascending) and rows_build_range with the label source at
 // row a; *labels += the range's labels.  The device holds the records plus
 // ONE range's labels.
-struct RowsFrom;
+struct RowsFrom {
+    Ctx range;  // the range handed to rows_build_range: the shape, this range's label source
+    hipStream_t s = nullptr;
+    uint32_t m = 0;
+    LabelNode *d_shape = nullptr;
+    uint16_t *d_inv = nullptr;     // column -> pre-order leaf index
+    uint32_t *d_status = nullptr;  // [0] the loaders' status bits, [1] the longest row (rows_from_cols.hip)
+    Workspace off, cols, keys, pairs, pairs2, sort;
+    std::vector<uint32_t> h_off;
+    // the loader from sparse columns (rows_from_cols.hip): pre-order leaf index
+    // -> column, the staged slices (pinned ids, offsets, work list)
+    std::vector<uint32_t> perm;
+    Workspace soff, work;
+    uint32_t *h_ids = nullptr;
+    size_t h_ids_cap = 0;
+    std::vector<uint32_t> h_soff;
+    std::vector<ColsWork> h_work;
+};
 int rows_from_begin(const Tree &shape, hipStream_t s, RowsFrom **out);
 int rows_from_range(RowsFrom *rf, RowsBuild *rb, const uint64_t *offsets, const uint32_t *cols, uint64_t a, uint64_t b,
                     uint64_t *labels);
@@ -525,6 +543,22 @@ int rows_counts_range(const LabelRows &rows, uint64_t num_rows, uint32_t num_dno
 // device bytes one range of `rows` rows and `labels` labels takes beside the
 // records (the sizing of the ranges, capi.cpp), and the most labels of a range
 uint64_t rows_from_range_bytes(uint64_t rows, uint64_t labels);
+// the same from sparse columns (rows_from_cols.hip): the
+// slices [cur[c], ends[c]) of the rows [a, b) (cols_host.hpp) staged in
+// pre-order, composed into (local row << 16 | key) pairs, sorted stably by
+// row and split into the keys and offsets rows_from_load ends with; *labels =
+// the range's labels.  An id outside the range or a slice that does not
+// ascend strictly -> MBRWT_ERR_INVALID; a row of more than 32,767 labels ->
+// MBRWT_ERR_UNSUPPORTED.  cols_from_range: the load, then rows_build_range.
+int cols_from_load(RowsFrom *rf, const ColsView &v, const std::vector<uint64_t> &cur,
+                   const std::vector<uint64_t> &ends, uint64_t a, uint64_t b, LabelRows *rows, uint64_t *labels);
+int cols_from_range(RowsFrom *rf, RowsBuild *rb, const ColsView &v, const std::vector<uint64_t> &cur,
+                    const std::vector<uint64_t> &ends, uint64_t a, uint64_t b, uint64_t *labels);
+// binary_grouping_greedy over the row sample gathered from sparse columns
+// (build.hip): sample slot k = row greedy_sample_rows(n)[k], every row its
+// own slot up to 10^6 rows (then every id is checked)
+int greedy_shape_from_sparse_columns(const ColsView &v, int device, std::vector<uint32_t> &num_children,
+                                     std::vector<uint32_t> &first_child, std::vector<uint32_t> &leaf_column);
 constexpr uint64_t kRowsFromMaxLabels = 0x7FFFFFFFull;  // (the device sort counts its items in an int)
 // launch grid of a grid-stride kernel over `items`: workgroups of 256
 // threads, one thread per item up to 65536 workgroups

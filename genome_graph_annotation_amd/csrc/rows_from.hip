@@ -115,21 +115,11 @@ __global__ __launch_bounds__(256) void k_rows_sorted(const uint64_t *__restrict_
 
 }  // namespace
 
-struct RowsFrom {
-    Ctx range;  // the range handed to rows_build_range: the shape, this range's label source
-    hipStream_t s = nullptr;
-    uint32_t m = 0;
-    LabelNode *d_shape = nullptr;
-    uint16_t *d_inv = nullptr;  // column -> pre-order leaf index
-    uint32_t *d_status = nullptr;
-    Workspace off, cols, keys, pairs, pairs2, sort;
-    std::vector<uint32_t> h_off;
-};
-
 void rows_from_end(RowsFrom *rf) {
     if (!rf) return;
-    for (Workspace *w : {&rf->off, &rf->cols, &rf->keys, &rf->pairs, &rf->pairs2, &rf->sort})
+    for (Workspace *w : {&rf->off, &rf->cols, &rf->keys, &rf->pairs, &rf->pairs2, &rf->sort, &rf->soff, &rf->work})
         if (w->buf) (void)hipFree(w->buf);
+    if (rf->h_ids) (void)hipHostFree(rf->h_ids);
     if (rf->d_shape) (void)hipFree(rf->d_shape);
     if (rf->d_inv) (void)hipFree(rf->d_inv);
     if (rf->d_status) (void)hipFree(rf->d_status);
@@ -177,10 +167,14 @@ int rows_from_begin(const Tree &shape, hipStream_t s, RowsFrom **out) {
         t = LabelNode{dn.first_child, dn.arity, tab[dn.first_child].lo, tab[dn.first_child + dn.arity - 1].hi};
     }
     std::vector<uint16_t> inv(m);
-    for (uint64_t k = 0; k < m; ++k) inv[shape.label_perm.empty() ? k : shape.label_perm[k]] = (uint16_t)k;
+    rf->perm.resize(m);
+    for (uint64_t k = 0; k < m; ++k) {
+        rf->perm[k] = shape.label_perm.empty() ? (uint32_t)k : shape.label_perm[k];
+        inv[rf->perm[k]] = (uint16_t)k;
+    }
     MBRWT_HIP(hipMalloc(&rf->d_shape, D * sizeof(LabelNode)));
     MBRWT_HIP(hipMalloc(&rf->d_inv, m * 2));
-    MBRWT_HIP(hipMalloc(&rf->d_status, 4));
+    MBRWT_HIP(hipMalloc(&rf->d_status, 8));
     MBRWT_HIP(hipMemcpy(rf->d_shape, tab.data(), D * sizeof(LabelNode), hipMemcpyHostToDevice));
     MBRWT_HIP(hipMemcpy(rf->d_inv, inv.data(), m * 2, hipMemcpyHostToDevice));
     guard.p = nullptr;

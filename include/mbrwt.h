@@ -201,6 +201,44 @@ typedef struct mbrwt_rows_desc {
 int mbrwt_create_from_rows(const mbrwt_rows_desc *desc, const mbrwt_shape_desc *shape, uint32_t arity, int device,
                            mbrwt_ctx **out);
 
+/*
+ * The same build from SPARSE COLUMNS: per column the
+ * strictly ascending ids of its set rows -- the form the reference holds its
+ * data in before a BRWT conversion (ColumnCompressed::data(), one bit vector
+ * per label; bit_vector::call_ones gives a column's ids in this order).  The
+ * rows are transposed on the device, range of rows by range of rows: every
+ * column's slice of ids in the range is staged (u32, relative to the range's
+ * first row), composed with the column's pre-order index, sorted stably by
+ * row and handed to the record builders of mbrwt_create_from_rows.  The
+ * context is the one mbrwt_create_from_rows gives on the same matrix: the
+ * same image bytes, mbrwt_rows_stats, mbrwt_tree_export and answers.
+ *
+ * Shape, arity, layout (always ROWS; NODES, BOTH: MBRWT_ERR_UNSUPPORTED),
+ * the record options of the calling thread, the limits and the empty
+ * matrices are those of mbrwt_create_from_rows.  Ranges are multiples of
+ * 360,360 rows sized like its ranges from the free device memory (here 24
+ * bytes per label and 4 per row), at most 2^31 - 1 labels each;
+ * MBRWT_BUILD_ROWS_RANGE fixes the size.
+ * rows: u64 ids; rows32: the same as u32 (num_rows <= 2^32); exactly one of
+ * the two is non-null (both null only without any label).
+ * MBRWT_ERR_INVALID: a row id >= num_rows, ids of a column that do not ascend
+ * strictly (unsorted, or a row twice) -- both found on the device, in the
+ * range that holds them --; offsets[0] != 0, descending offsets, a null
+ * offsets array, both rows and rows32, neither with labels present, rows32
+ * with num_rows > 2^32 -- on the host before any device call; a null desc or
+ * out, with or without a GPU.  A row of more than 32,767 labels:
+ * MBRWT_ERR_UNSUPPORTED (seen on the device, from the range's row lengths).
+ * A failed build frees everything it allocated.
+ */
+typedef struct mbrwt_sparse_columns_desc {
+    uint64_t num_rows, num_columns;
+    const uint64_t *offsets; /* num_columns + 1, offsets[0] = 0, ascending */
+    const uint64_t *rows;    /* column c: rows[offsets[c] .. offsets[c+1]), strictly ascending; or NULL */
+    const uint32_t *rows32;  /* the same as u32 (num_rows <= 2^32); exactly one of rows / rows32 non-null */
+} mbrwt_sparse_columns_desc;
+int mbrwt_create_from_sparse_columns(const mbrwt_sparse_columns_desc *desc, const mbrwt_shape_desc *shape,
+                                     uint32_t arity, int device, mbrwt_ctx **out);
+
 void mbrwt_destroy(mbrwt_ctx *ctx);
 
 /* A second query context over the SAME device image (no copy): its own
@@ -472,6 +510,20 @@ int mbrwt_tree_relax_shape(const mbrwt_shape_desc *shape, const uint64_t *counts
                            mbrwt_tree **out);
 int mbrwt_tree_shape_from_rows(const mbrwt_rows_desc *desc, int partitioner, uint32_t arity,
                                uint64_t relax_max_arity, int device, mbrwt_tree **out);
+/* The same two from sparse columns, with the arguments,
+ * limits and statuses of mbrwt_create_from_sparse_columns:
+ * mbrwt_sparse_columns_node_counts equals mbrwt_rows_node_counts of the same
+ * matrix (the ranges transposed on the device, every id checked);
+ * mbrwt_tree_shape_from_sparse_columns equals mbrwt_tree_shape_from_rows node
+ * for node.  The greedy partitioner's sample (the reference's 10^6 sampled
+ * rows; every row up to 10^6 rows) is intersected with every column's ids on
+ * the host and scattered into the sample columns on the device; it checks the
+ * ids when every row is sampled, the counts pass (relax_max_arity > 1)
+ * always. */
+int mbrwt_sparse_columns_node_counts(const mbrwt_sparse_columns_desc *desc, const mbrwt_shape_desc *shape,
+                                     uint32_t arity, int device, uint64_t *counts);
+int mbrwt_tree_shape_from_sparse_columns(const mbrwt_sparse_columns_desc *desc, int partitioner, uint32_t arity,
+                                         uint64_t relax_max_arity, int device, mbrwt_tree **out);
 const mbrwt_tree_desc *mbrwt_tree_get_desc(const mbrwt_tree *tree); /* valid until mbrwt_tree_free */
 void mbrwt_tree_free(mbrwt_tree *tree);
 int mbrwt_load(const uint8_t *bytes, uint64_t len, uint64_t *consumed, int device, mbrwt_ctx **out);

@@ -28,6 +28,8 @@ ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--relax", type=int, default=0, help="then BRWTOptimizer::relax with this max arity")
 ap.add_argument("--from-rows", action="store_true",
                 help="the same matrix through from_rows (CSR rows) and from_columns(layout='rows'), reps alternating")
+ap.add_argument("--from-sparse-columns", action="store_true",
+                help="as --from-rows, with from_sparse_columns (ascending row ids per column) alternating with the two")
 ap.add_argument("--greedy", action="store_true",
                 help="binary_grouping_greedy instead of the basic partitioner; with --from-rows the shape comes from "
                      "the rows (shape_from_rows) and its steps are timed one by one as well")
@@ -57,6 +59,14 @@ def csr_rows(cols, n):
     return np.cumsum(off, dtype=np.uint64), np.concatenate(parts)
 
 
+def sparse_columns(cols, n):
+    """The matrix's columns as ascending row ids (u32) with their offsets, from its column words."""
+    ids = [np.flatnonzero(np.unpackbits(c.view(np.uint8), bitorder="little")[:n]).astype(np.uint32) for c in cols]
+    off = np.zeros(len(ids) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(i) for i in ids])
+    return off, np.concatenate(ids) if ids else np.zeros(0, dtype=np.uint32)
+
+
 class LowWater:
     """The low-water mark of hipMemGetInfo's free bytes while the block runs
     (sampled around it and by a thread during it)."""
@@ -82,35 +92,39 @@ class LowWater:
         self.low = min(self.low, self._info())
 
 
-if a.from_rows:
+if a.from_rows or a.from_sparse_columns:
     import torch
     torch.cuda.init()
     off, lab = csr_rows(cols, n)
     kw = dict(partitioner=PART, relax_max_arity=a.relax)
+    build = {"from_rows": lambda: BRWTDevice.from_rows(off, lab, m, arity=a.arity, **kw),
+             "from_columns": lambda: BRWTDevice.from_columns(cols, n, a.arity, layout="rows", **kw)}
+    names = ["from_rows", "from_columns"]
+    if a.from_sparse_columns:
+        coff, cids = sparse_columns(cols, n)
+        build["from_sparse_columns"] = lambda: BRWTDevice.from_sparse_columns(coff, cids, n, m, arity=a.arity, **kw)
+        names.insert(0, "from_sparse_columns")
+        few = min(m, 16)
+        BRWTDevice.from_sparse_columns(coff[: few + 1], cids[: int(coff[few])], n, few, arity=a.arity, **kw).close()
     BRWTDevice.from_rows(off[:1025], lab[: int(off[1024])], m, arity=a.arity, **kw).close()  # warm-up
     BRWTDevice.from_columns(cols[: min(m, 16)], n, a.arity, layout="rows", **kw).close()
-    res = {"from_rows": {"s": [], "used": []}, "from_columns": {"s": [], "used": []}}
+    res = {name: {"s": [], "used": []} for name in names}
+    rows = np.random.default_rng(1).integers(0, n, 200_000).astype(np.uint64)
     for _ in range(a.reps):
-        for name in ("from_rows", "from_columns"):
+        for name in names:
             with LowWater() as lw:
                 t0 = time.perf_counter()
-                built = (BRWTDevice.from_rows(off, lab, m, arity=a.arity, **kw) if name == "from_rows" else
-                         BRWTDevice.from_columns(cols, n, a.arity, layout="rows", **kw))
+                built = build[name]()
                 res[name]["s"].append(time.perf_counter() - t0)
             res[name]["used"].append(int(lw.before - lw.low))
             res[name]["image_bytes"] = int(built.device_bytes())
             res[name]["stats"] = built.rows_stats()
             res[name]["shape"] = [built.export()[k].tolist() for k in ("num_children", "first_child", "leaf_column")]
-            if name == "from_rows":
-                rows = np.random.default_rng(1).integers(0, n, 200_000).astype(np.uint64)
-                got = built.get_rows(rows)
-            else:
-                want = built.get_rows(rows)
+            res[name]["rows"] = built.get_rows(rows)
             built.close()
-    same = (res["from_rows"]["image_bytes"] == res["from_columns"]["image_bytes"]
-            and res["from_rows"]["stats"] == res["from_columns"]["stats"]
-            and res["from_rows"]["shape"] == res["from_columns"]["shape"]
-            and all(np.array_equal(x, y) for x, y in zip(got, want)))
+    want = res["from_columns"]
+    same = all(r["image_bytes"] == want["image_bytes"] and r["stats"] == want["stats"] and r["shape"] == want["shape"]
+               and all(np.array_equal(x, y) for x, y in zip(r["rows"], want["rows"])) for r in res.values())
     steps = {}
     if a.greedy or a.relax:  # the steps of from_rows' shape, each on its own (their sum: one more full run)
         from genome_graph_annotation_amd.brwt import node_counts_from_rows, relax_shape, shape_from_rows
@@ -128,12 +142,32 @@ if a.from_rows:
             for k, v in zip(steps, (t1 - t0, t2 - t1, t3 - t2, t4 - t3)):
                 steps[k].append(v)
         steps = {k: {"median_s": float(np.median(v)), "runs_s": v} for k, v in steps.items()}
+    sparse_steps = {}
+    if a.from_sparse_columns and (a.greedy or a.relax):  # the same steps from the sparse columns
+        from genome_graph_annotation_amd.brwt import node_counts_from_sparse_columns, shape_from_sparse_columns
+        sparse_steps = {"partition_s": [], "counts_s": [], "relax_s": [], "records_s": []}
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            plain = shape_from_sparse_columns(coff, cids, n, m, PART, a.arity)
+            t1 = time.perf_counter()
+            counts = node_counts_from_sparse_columns(coff, cids, n, m, shape=plain)
+            t2 = time.perf_counter()
+            shape = relax_shape(plain, counts, a.relax)
+            t3 = time.perf_counter()
+            BRWTDevice.from_sparse_columns(coff, cids, n, m, shape=shape).close()
+            t4 = time.perf_counter()
+            for k, v in zip(sparse_steps, (t1 - t0, t2 - t1, t3 - t2, t4 - t3)):
+                sparse_steps[k].append(v)
+        sparse_steps = {k: {"median_s": float(np.median(v)), "runs_s": v} for k, v in sparse_steps.items()}
     print(json.dumps({
-        "metric": "row-record build from host data to a queryable context: from_rows (CSR rows) against "
+        "metric": "row-record build from host data to a queryable context: "
+                  + ("from_sparse_columns (ascending row ids per column), " if a.from_sparse_columns else "")
+                  + "from_rows (CSR rows) against "
                   "from_columns(layout='rows') (dense columns), reps alternating in one process",
         "config": {"rows": n, "columns": m, "density": a.density, "arity": a.arity, "relations": int(len(lab)),
                    "partitioner": PART, "relax_max_arity": a.relax, "nodes": len(res["from_rows"]["shape"][0])},
         "from_rows_steps": steps,
+        **({"from_sparse_columns_steps": sparse_steps} if a.from_sparse_columns else {}),
         **{name: {"median_s": float(np.median(r["s"])), "runs_s": r["s"], "image_bytes": r["image_bytes"],
                   "device_low_water_used_bytes": int(max(r["used"])), "low_water_runs": r["used"]}
            for name, r in res.items()},
