@@ -174,8 +174,7 @@ def basic_shape(num_columns, arity):
     BRWTDevice.synthetic_shaped and BRWTDevice.from_rows take."""
     h = C.c_void_p()
     L.check(L.lib().mbrwt_tree_basic_shape(int(num_columns), int(arity), C.byref(h)), "mbrwt_tree_basic_shape")
-    t = _tree_dict(h)
-    return dict(num_children=t["num_children"], first_child=t["first_child"], leaf_column=t["leaf_column"])
+    return _shape_dict(h)
 
 
 def _shape_dict(handle):
@@ -202,23 +201,44 @@ def _shape_desc(shape):
     return L.ShapeDesc(len(nc), _p(nc, C.c_uint32), _p(fc, C.c_uint32), _p(lc, C.c_uint32)), (nc, fc, lc)
 
 
+def _opt_shape_desc(shape):
+    """(pointer to the mbrwt_shape_desc of `shape`, what it points into), or
+    (None, None) without a shape."""
+    if shape is None:
+        return None, None
+    s, keep = _shape_desc(shape)
+    return C.byref(s), (s, keep)
+
+
+def _node_counts(fn, make_desc, source, shape, arity, device):
+    """The per-node row counts `fn` (mbrwt_rows_node_counts,
+    mbrwt_sparse_columns_node_counts) gives on the matrix make_desc(*source)
+    describes; num_columns is the last of `source`."""
+    d, keep = make_desc(*source)
+    sd, keep_s = _opt_shape_desc(shape)
+    nodes = len((shape if shape is not None else basic_shape(source[-1], arity))["num_children"])
+    counts = np.zeros(max(1, nodes), dtype=np.uint64)
+    L.check(getattr(L.lib(), fn)(C.byref(d), sd, int(arity), device, _p(counts, C.c_uint64)), fn)
+    del keep, keep_s
+    return counts[:nodes]
+
+
+def _shape_from(fn, make_desc, source, partitioner, arity, relax_max_arity, device):
+    """The shape dict `fn` (mbrwt_tree_shape_from_rows,
+    mbrwt_tree_shape_from_sparse_columns) gives on the matrix make_desc(*source) describes."""
+    d, keep = make_desc(*source)
+    part = L.PARTITIONERS[partitioner] if isinstance(partitioner, str) else int(partitioner)
+    h = C.c_void_p()
+    L.check(getattr(L.lib(), fn)(C.byref(d), part, int(arity), int(relax_max_arity), device, C.byref(h)), fn)
+    del keep
+    return _shape_dict(h)
+
+
 def node_counts_from_rows(offsets, cols, num_columns, shape=None, arity=8, device=0):
     """Per BFS node of `shape` (None: basic_shape(num_columns, arity)) the
     number of CSR rows with a label below it (mbrwt_rows_node_counts): a
     leaf's column popcount, the root's non-empty rows.  uint64 array."""
-    d, keep = _rows_desc(offsets, cols, num_columns)
-    sd, keep_s = None, None
-    if shape is not None:
-        s, keep_s = _shape_desc(shape)
-        sd = C.byref(s)
-        nodes = len(keep_s[0])
-    else:
-        nodes = len(basic_shape(num_columns, arity)["num_children"])
-    counts = np.zeros(max(1, nodes), dtype=np.uint64)
-    L.check(L.lib().mbrwt_rows_node_counts(C.byref(d), sd, int(arity), device, _p(counts, C.c_uint64)),
-            "mbrwt_rows_node_counts")
-    del keep, keep_s
-    return counts[:nodes]
+    return _node_counts("mbrwt_rows_node_counts", _rows_desc, (offsets, cols, num_columns), shape, arity, device)
 
 
 def relax_shape(shape, counts, max_arity):
@@ -243,13 +263,8 @@ def shape_from_rows(offsets, cols, num_columns, partitioner="basic", arity=8, re
     (binary_grouping_greedy over the row sample), then BRWTOptimizer::relax
     over all rows when relax_max_arity > 1.  Returns the shape dict
     BRWTDevice.from_rows and BRWTDevice.synthetic_shaped take."""
-    d, keep = _rows_desc(offsets, cols, num_columns)
-    part = L.PARTITIONERS[partitioner] if isinstance(partitioner, str) else int(partitioner)
-    h = C.c_void_p()
-    L.check(L.lib().mbrwt_tree_shape_from_rows(C.byref(d), part, int(arity), int(relax_max_arity), device,
-                                               C.byref(h)), "mbrwt_tree_shape_from_rows")
-    del keep
-    return _shape_dict(h)
+    return _shape_from("mbrwt_tree_shape_from_rows", _rows_desc, (offsets, cols, num_columns), partitioner, arity,
+                       relax_max_arity, device)
 
 
 def _sparse_columns_desc(col_offsets, col_rows, num_rows, num_columns):
@@ -272,32 +287,16 @@ def node_counts_from_sparse_columns(col_offsets, col_rows, num_rows, num_columns
     """node_counts_from_rows of the matrix given as sparse columns: column c
     holds the rows col_rows[col_offsets[c]:col_offsets[c + 1]], strictly
     ascending (mbrwt_sparse_columns_node_counts).  uint64 array."""
-    d, keep = _sparse_columns_desc(col_offsets, col_rows, num_rows, num_columns)
-    sd, keep_s = None, None
-    if shape is not None:
-        s, keep_s = _shape_desc(shape)
-        sd = C.byref(s)
-        nodes = len(keep_s[0])
-    else:
-        nodes = len(basic_shape(num_columns, arity)["num_children"])
-    counts = np.zeros(max(1, nodes), dtype=np.uint64)
-    L.check(L.lib().mbrwt_sparse_columns_node_counts(C.byref(d), sd, int(arity), device, _p(counts, C.c_uint64)),
-            "mbrwt_sparse_columns_node_counts")
-    del keep, keep_s
-    return counts[:nodes]
+    return _node_counts("mbrwt_sparse_columns_node_counts", _sparse_columns_desc,
+                        (col_offsets, col_rows, num_rows, num_columns), shape, arity, device)
 
 
 def shape_from_sparse_columns(col_offsets, col_rows, num_rows, num_columns, partitioner="basic", arity=8,
                               relax_max_arity=0, device=0):
     """shape_from_rows of the matrix given as sparse columns
     (mbrwt_tree_shape_from_sparse_columns): the same shape dict, node for node."""
-    d, keep = _sparse_columns_desc(col_offsets, col_rows, num_rows, num_columns)
-    part = L.PARTITIONERS[partitioner] if isinstance(partitioner, str) else int(partitioner)
-    h = C.c_void_p()
-    L.check(L.lib().mbrwt_tree_shape_from_sparse_columns(C.byref(d), part, int(arity), int(relax_max_arity), device,
-                                                         C.byref(h)), "mbrwt_tree_shape_from_sparse_columns")
-    del keep
-    return _shape_dict(h)
+    return _shape_from("mbrwt_tree_shape_from_sparse_columns", _sparse_columns_desc,
+                       (col_offsets, col_rows, num_rows, num_columns), partitioner, arity, relax_max_arity, device)
 
 
 @contextlib.contextmanager
@@ -364,17 +363,14 @@ class BRWTDevice:
         """The synthetic law over a given tree shape (mbrwt_create_synthetic_shaped):
         `shape` = dict with num_children, first_child, leaf_column (BFS), e.g.
         the export of a greedy + relaxed tree."""
-        lib = L.lib()
-        nc = np.ascontiguousarray(shape["num_children"], dtype=np.uint32)
-        fc = np.ascontiguousarray(shape["first_child"], dtype=np.uint32)
-        lc = np.ascontiguousarray(shape["leaf_column"], dtype=np.uint32)
-        m = int((nc == 0).sum())
+        sd, keep = _shape_desc(shape)
+        m = int((keep[0] == 0).sum())
         d = L.SynthDesc(num_rows, m, float(density), 0, seed)
-        sd = L.ShapeDesc(len(nc), _p(nc, C.c_uint32), _p(fc, C.c_uint32), _p(lc, C.c_uint32))
         h = C.c_void_p()
         with build_layout(layout):
-            L.check(lib.mbrwt_create_synthetic_shaped(C.byref(d), C.byref(sd), device, C.byref(h)),
+            L.check(L.lib().mbrwt_create_synthetic_shaped(C.byref(d), C.byref(sd), device, C.byref(h)),
                     "mbrwt_create_synthetic_shaped")
+        del keep
         return cls(h)
 
     @classmethod
@@ -416,29 +412,8 @@ class BRWTDevice:
         relax_max_arity > 1: the shape is shape_from_rows(...) of these rows
         (not together with `shape`).  No node image and no dense column is
         built; the context's layout is 'rows'."""
-        if partitioner != "basic" or relax_max_arity:
-            if shape is not None:
-                raise ValueError("give a shape, or a partitioner / relax_max_arity to compute one: not both")
-            shape = shape_from_rows(offsets, cols, num_columns, partitioner, arity, relax_max_arity, device)
-            if len(shape["num_children"]) == 0:  # no column: the call below builds the empty context
-                shape = None
-        lib = L.lib()
-        off = np.ascontiguousarray(offsets, dtype=np.uint64)
-        if off.size == 0:
-            raise ValueError("offsets needs num_rows + 1 entries")
-        cl = np.ascontiguousarray(cols, dtype=np.uint32)
-        if cl.size == 0:
-            cl = np.zeros(1, dtype=np.uint32)
-        d = L.RowsDesc(off.size - 1, int(num_columns), _p(off, C.c_uint64), _p(cl, C.c_uint32))
-        sd = None
-        if shape is not None:
-            nc = np.ascontiguousarray(shape["num_children"], dtype=np.uint32)
-            fc = np.ascontiguousarray(shape["first_child"], dtype=np.uint32)
-            lc = np.ascontiguousarray(shape["leaf_column"], dtype=np.uint32)
-            sd = C.byref(L.ShapeDesc(len(nc), _p(nc, C.c_uint32), _p(fc, C.c_uint32), _p(lc, C.c_uint32)))
-        h = C.c_void_p()
-        L.check(lib.mbrwt_create_from_rows(C.byref(d), sd, int(arity), device, C.byref(h)), "mbrwt_create_from_rows")
-        return cls(h)
+        return cls._from_source("mbrwt_create_from_rows", shape_from_rows, _rows_desc, (offsets, cols, num_columns),
+                                arity, shape, device, partitioner, relax_max_arity)
 
     @classmethod
     def from_sparse_columns(cls, col_offsets, col_rows, num_rows, num_columns, arity=8, shape=None, device=0,
@@ -449,21 +424,24 @@ class BRWTDevice:
         `shape`, `arity`, `partitioner` and `relax_max_arity` as in from_rows
         (the shape computed by shape_from_sparse_columns); the context equals
         from_rows of the same matrix."""
+        return cls._from_source("mbrwt_create_from_sparse_columns", shape_from_sparse_columns, _sparse_columns_desc,
+                                (col_offsets, col_rows, num_rows, num_columns), arity, shape, device, partitioner,
+                                relax_max_arity)
+
+    @classmethod
+    def _from_source(cls, fn, shape_of, make_desc, source, arity, shape, device, partitioner, relax_max_arity):
+        """from_rows / from_sparse_columns: the context `fn` builds of the matrix
+        make_desc(*source) describes, under `shape` or the shape shape_of computes."""
         if partitioner != "basic" or relax_max_arity:
             if shape is not None:
                 raise ValueError("give a shape, or a partitioner / relax_max_arity to compute one: not both")
-            shape = shape_from_sparse_columns(col_offsets, col_rows, num_rows, num_columns, partitioner, arity,
-                                              relax_max_arity, device)
+            shape = shape_of(*source, partitioner, arity, relax_max_arity, device)
             if len(shape["num_children"]) == 0:  # no column: the call below builds the empty context
                 shape = None
-        d, keep = _sparse_columns_desc(col_offsets, col_rows, num_rows, num_columns)
-        sd, keep_s = None, None
-        if shape is not None:
-            s, keep_s = _shape_desc(shape)
-            sd = C.byref(s)
+        d, keep = make_desc(*source)
+        sd, keep_s = _opt_shape_desc(shape)
         h = C.c_void_p()
-        L.check(L.lib().mbrwt_create_from_sparse_columns(C.byref(d), sd, int(arity), device, C.byref(h)),
-                "mbrwt_create_from_sparse_columns")
+        L.check(getattr(L.lib(), fn)(C.byref(d), sd, int(arity), device, C.byref(h)), fn)
         del keep, keep_s
         return cls(h)
 

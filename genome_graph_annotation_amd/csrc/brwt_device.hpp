@@ -205,13 +205,9 @@ class BRWTDevice : public BinaryMatrix {
                                              uint64_t num_columns, uint64_t relax_max_arity = 0, int device = 0) {
         if (offsets.empty()) throw std::invalid_argument("build_from_rows_greedy: offsets needs num_rows + 1 entries");
         const mbrwt_rows_desc d{offsets.size() - 1, num_columns, offsets.data(), cols.data()};
-        mbrwt_tree *t = nullptr;
-        check_status(mbrwt_tree_shape_from_rows(&d, MBRWT_PARTITIONER_GREEDY, 2, relax_max_arity, device, &t),
-                     "mbrwt_tree_shape_from_rows");
-        std::unique_ptr<mbrwt_tree, void (*)(mbrwt_tree *)> owned(t, mbrwt_tree_free);
-        const mbrwt_tree_desc *td = mbrwt_tree_get_desc(t);
-        const mbrwt_shape_desc shape{td->num_nodes, td->num_children, td->first_child, td->leaf_column};
-        return build_from_rows(offsets, cols, num_columns, 2, td->num_nodes ? &shape : nullptr, device);
+        return build_under_greedy_shape(
+            d, mbrwt_tree_shape_from_rows, "mbrwt_tree_shape_from_rows", relax_max_arity, device,
+            [&](const mbrwt_shape_desc *shape) { return build_from_rows(offsets, cols, num_columns, 2, shape, device); });
     }
 
     // The same two from sparse columns (mbrwt_create_from_sparse_columns):
@@ -239,14 +235,10 @@ class BRWTDevice : public BinaryMatrix {
         if (offsets.empty())
             throw std::invalid_argument("build_from_sparse_columns_greedy: offsets needs num_columns + 1 entries");
         const mbrwt_sparse_columns_desc d{num_rows, offsets.size() - 1, offsets.data(), rows.data(), nullptr};
-        mbrwt_tree *t = nullptr;
-        check_status(mbrwt_tree_shape_from_sparse_columns(&d, MBRWT_PARTITIONER_GREEDY, 2, relax_max_arity, device,
-                                                          &t),
-                     "mbrwt_tree_shape_from_sparse_columns");
-        std::unique_ptr<mbrwt_tree, void (*)(mbrwt_tree *)> owned(t, mbrwt_tree_free);
-        const mbrwt_tree_desc *td = mbrwt_tree_get_desc(t);
-        const mbrwt_shape_desc shape{td->num_nodes, td->num_children, td->first_child, td->leaf_column};
-        return build_from_sparse_columns(offsets, rows, num_rows, 2, td->num_nodes ? &shape : nullptr, device);
+        return build_under_greedy_shape(d, mbrwt_tree_shape_from_sparse_columns, "mbrwt_tree_shape_from_sparse_columns",
+                                        relax_max_arity, device, [&](const mbrwt_shape_desc *shape) {
+                                            return build_from_sparse_columns(offsets, rows, num_rows, 2, shape, device);
+                                        });
     }
 
     // a query handle over the same device image (mbrwt_ctx_clone): one per
@@ -497,6 +489,19 @@ class BRWTDevice : public BinaryMatrix {
     };
     std::shared_ptr<mbrwt_ctx> ctx_{nullptr, Deleter()};
     int device_ = 0;
+
+    // build(shape) under the greedy (+ relaxed) shape shape_from(&d, ...)
+    // computes of the matrix d describes; shape = nullptr when it has no column
+    template <class Desc, class ShapeFrom, class Build>
+    static BRWTDevice build_under_greedy_shape(const Desc &d, ShapeFrom shape_from, const char *where,
+                                               uint64_t relax_max_arity, int device, Build build) {
+        mbrwt_tree *t = nullptr;
+        check_status(shape_from(&d, MBRWT_PARTITIONER_GREEDY, 2, relax_max_arity, device, &t), where);
+        std::unique_ptr<mbrwt_tree, void (*)(mbrwt_tree *)> owned(t, mbrwt_tree_free);
+        const mbrwt_tree_desc *td = mbrwt_tree_get_desc(t);
+        const mbrwt_shape_desc shape{td->num_nodes, td->num_children, td->first_child, td->leaf_column};
+        return build(td->num_nodes ? &shape : nullptr);
+    }
 
   public:
     BRWTDevice(const BRWTDevice &) = default;

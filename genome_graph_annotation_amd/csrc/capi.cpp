@@ -22,6 +22,20 @@ int hip_fail(hipError_t e, const char *what) {
     return (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) ? MBRWT_ERR_NOMEM : MBRWT_ERR_DEVICE;
 }
 
+// f() for the extern "C" function `name`: no exception crosses the ABI
+template <class F>
+static int guarded(const char *name, F &&f) {
+    try {
+        return f();
+    } catch (const std::bad_alloc &) {
+        set_error("host allocation failed");
+        return MBRWT_ERR_NOMEM;
+    } catch (...) {
+        set_error(std::string("unexpected exception in ") + name);
+        return MBRWT_ERR_INVALID;
+    }
+}
+
 static int init_query_state(Ctx &c);
 
 static int upload_tables(Ctx &c) {
@@ -358,227 +372,6 @@ static int create_rows_ranged(int device, uint64_t num_rows, uint64_t num_column
         kNoLayoutHook);
 }
 
-// Row records straight from CSR rows under a tree shape (rows_from.hip;
-// DESIGN.md §11b): no node image at all, so the device holds the records
-// plus ONE range's labels.  Ranges are multiples of kRowsAlign rows; the
-// first (at most kRowsFirstRange rows) decides the record code and layout;
-// every range is cut from `offsets` so that its labels fit the memory left
-// (the 8 GiB reserve of create_rows_ranged) and the device sort's item count;
-// MBRWT_BUILD_ROWS_RANGE fixes the size.
-struct RowsFromEnd {
-    void operator()(RowsFrom *rf) const { rows_from_end(rf); }
-};
-// the largest range [a, a + k kRowsAlign), k kRowsAlign <= R, of the n rows of
-// `off` whose labels fit the free device memory less the reserve and
-// `pending` (the bytes the build will still allocate); a fixed range size
-// (MBRWT_BUILD_ROWS_RANGE) is taken as it is
-static double range_budget(uint64_t pending) {
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    const double left = (double)free_b - 8.0 * (1ull << 30) - (double)pending;
-    return std::max(left, (double)free_b / 8) / 1.2;
-}
-static uint64_t cut_rows_range(const uint64_t *off, uint64_t n, uint64_t a, uint64_t R, uint64_t pending) {
-    if (build_tuning().rows_range != 0) return std::min(n, a + R);
-    const double budget = range_budget(pending);
-    return cut_range_fit(n, a, R, kRowsAlign, [&](uint64_t e) {
-        const uint64_t L = off[e] - off[a];
-        return L <= kRowsFromMaxLabels && (double)rows_from_range_bytes(e - a, L) <= budget;
-    });
-}
-
-static int create_from_rows(const mbrwt_rows_desc &desc, const Tree &shape, int device, mbrwt_ctx **out) {
-    const uint64_t n = desc.num_rows;
-    const uint64_t *off = desc.offsets;
-    return create_common(
-        device, out,
-        [&](Ctx &c) {
-            c.tree = shape;
-            c.tree.num_rows = n;
-            RowsFrom *rfp = nullptr;
-            if (int rc = rows_from_begin(c.tree, c.stream, &rfp)) return rc;
-            std::unique_ptr<RowsFrom, RowsFromEnd> rf(rfp);
-            // (auto_layout = false: there is no node image to fall back to)
-            RowsBuildPtr rb(rows_build_begin(c, n, kRowsAlign, false));
-            if (!rb) return (int)MBRWT_ERR_NOMEM;
-            const bool fixed = build_tuning().rows_range != 0;
-            for (uint64_t a = 0, b = 0; a < n; a = b) {
-                b = cut_rows_range(off, n, a,
-                                   fixed || a ? rows_range_rows() : std::min(rows_range_rows(), kRowsFirstRange),
-                                   fixed ? 0 : rows_build_pending_bytes(rb.get(), n - a));
-                if (int rc = rows_from_range(rf.get(), rb.get(), off, desc.cols, a, b, &c.tree.num_relations))
-                    return rc;  // (rb frees the build)
-            }
-            rf.reset();
-            if (int rc = rows_build_finish(rb.release())) return rc;
-            c.nodes_freed = true;
-            return (int)MBRWT_OK;
-        },
-        kNoLayoutHook);
-}
-
-// Per-node row counts under a tree shape (rows_counts.hip):
-// the ranges and the loader of the build without any record, so a range takes
-// the memory the records would; the counts accumulate on the device across
-// the ranges and come back once, dnode u + 1 of the shape table being BFS
-// node u.  The frame both sources share: the walk's limits, pre() (the
-// source's own host checks), the device, the stream, the loader and the
-// counters; ranges(rf, d_counts, stream) loads every range and counts it.
-template <class Pre, class Ranges>
-static int node_counts_over(const Tree &shape, int device, uint64_t *counts, Pre pre, Ranges ranges) {
-    const size_t D = shape.nodes.size();
-    // the walk's limits (rows_emit.hpp emit_label_masks): internal levels on a path
-    std::vector<uint32_t> level(D, 0);
-    for (size_t v = 1; v < D; ++v) {
-        const DevNode &dn = shape.nodes[v];
-        if (dn.kind == KIND_LEAF) continue;
-        if (v == 1) level[v] = 1;
-        if (level[v] > kRowsMaxHeight) {
-            set_error(rows_limits_message());
-            return MBRWT_ERR_UNSUPPORTED;
-        }
-        for (uint32_t c = 0; c < dn.arity; ++c) level[dn.first_child + c] = level[v] + 1;
-    }
-    if (int rc = pre()) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_error("no HIP device available");
-        return MBRWT_ERR_DEVICE;
-    }
-    if (device < 0 || device >= ndev) {
-        set_error("device index out of range");
-        return MBRWT_ERR_INVALID;
-    }
-    MBRWT_HIP(hipSetDevice(device));
-    struct Scope {
-        hipStream_t s = nullptr;
-        unsigned long long *d_counts = nullptr;
-        RowsFrom *rf = nullptr;
-        ~Scope() {
-            rows_from_end(rf);
-            if (d_counts) (void)hipFree(d_counts);
-            if (s) (void)hipStreamDestroy(s);
-        }
-    } sc;
-    MBRWT_HIP(hipStreamCreateWithFlags(&sc.s, hipStreamNonBlocking));
-    if (int rc = rows_from_begin(shape, sc.s, &sc.rf)) return rc;
-    MBRWT_HIP(hipMalloc(&sc.d_counts, D * sizeof(uint64_t)));
-    MBRWT_HIP(hipMemsetAsync(sc.d_counts, 0, D * sizeof(uint64_t), sc.s));
-    if (int rc = ranges(sc.rf, sc.d_counts, sc.s)) return rc;
-    std::vector<unsigned long long> h(D);
-    MBRWT_HIP(hipMemcpyAsync(h.data(), sc.d_counts, D * sizeof(uint64_t), hipMemcpyDeviceToHost, sc.s));
-    MBRWT_HIP(hipStreamSynchronize(sc.s));
-    for (size_t u = 0; u + 1 < D; ++u) counts[u] = h[u + 1];
-    return MBRWT_OK;
-}
-
-static int rows_node_counts(const mbrwt_rows_desc &desc, const Tree &shape, int device, uint64_t *counts) {
-    const uint64_t n = desc.num_rows;
-    const uint64_t *off = desc.offsets;
-    const uint32_t D = (uint32_t)shape.nodes.size();
-    return node_counts_over(
-        shape, device, counts,
-        [&]() {
-            for (uint64_t r = 0; r < n; ++r)
-                if (off[r + 1] - off[r] > 0x7FFFu) {
-                    set_error("row record deeper than the build walker supports, or a row of more than 32,767 labels");
-                    return (int)MBRWT_ERR_UNSUPPORTED;
-                }
-            return (int)MBRWT_OK;
-        },
-        [&](RowsFrom *rf, unsigned long long *d_counts, hipStream_t s) {
-            for (uint64_t a = 0, b = 0; a < n; a = b) {
-                b = cut_rows_range(off, n, a, rows_range_rows(), 0);
-                LabelRows rows;
-                if (int rc = rows_from_load(rf, off, desc.cols, a, b, &rows)) return rc;
-                if (int rc = rows_counts_range(rows, b - a, D, d_counts, s)) return rc;
-                // (the next load overwrites the range's buffers)
-                MBRWT_HIP(hipStreamSynchronize(s));
-            }
-            return (int)MBRWT_OK;
-        });
-}
-
-// The same two from sparse columns (rows_from_cols.hip): one
-// cursor per column walks the ranges; a range is cut from the cursors
-// (cols_host.hpp cut_cols_range: the labels of a candidate range by bisection
-// from every cursor) and its slices end where the next range's begin.
-static ColsView cols_view(const mbrwt_sparse_columns_desc &d) {
-    ColsView v;
-    v.num_rows = d.num_rows;
-    v.num_columns = d.num_columns;
-    v.offsets = d.offsets;
-    v.rows = d.rows;
-    v.rows32 = d.rows32;
-    return v;
-}
-struct ColsRanges {
-    ColsView v;
-    std::vector<uint64_t> cur, ends;
-    explicit ColsRanges(const mbrwt_sparse_columns_desc &d) : v(cols_view(d)), cur(d.offsets, d.offsets + d.num_columns) {}
-    // the range after a: [a, b), its slices [cur, ends)
-    uint64_t cut(uint64_t a, uint64_t R, uint64_t pending) {
-        const bool fixed = build_tuning().rows_range != 0;
-        const uint64_t b = cut_cols_range(v.num_rows, v.num_columns, a, R, kRowsAlign, fixed,
-                                          fixed ? 0.0 : range_budget(pending),
-                                          [&](uint64_t e) { return cols_cut_slices(v, cur, e, nullptr); });
-        cols_cut_slices(v, cur, b, &ends);
-        return b;
-    }
-    void advance() { cur.swap(ends); }
-};
-
-static int create_from_sparse_columns(const mbrwt_sparse_columns_desc &desc, const Tree &shape, int device,
-                                      mbrwt_ctx **out) {
-    const uint64_t n = desc.num_rows;
-    return create_common(
-        device, out,
-        [&](Ctx &c) {
-            c.tree = shape;
-            c.tree.num_rows = n;
-            RowsFrom *rfp = nullptr;
-            if (int rc = rows_from_begin(c.tree, c.stream, &rfp)) return rc;
-            std::unique_ptr<RowsFrom, RowsFromEnd> rf(rfp);
-            RowsBuildPtr rb(rows_build_begin(c, n, kRowsAlign, false));
-            if (!rb) return (int)MBRWT_ERR_NOMEM;
-            const bool fixed = build_tuning().rows_range != 0;
-            ColsRanges rg(desc);
-            for (uint64_t a = 0, b = 0; a < n; a = b) {
-                b = rg.cut(a, fixed || a ? rows_range_rows() : std::min(rows_range_rows(), kRowsFirstRange),
-                           fixed ? 0 : rows_build_pending_bytes(rb.get(), n - a));
-                if (int rc = cols_from_range(rf.get(), rb.get(), rg.v, rg.cur, rg.ends, a, b, &c.tree.num_relations))
-                    return rc;  // (rb frees the build)
-                rg.advance();
-            }
-            rf.reset();
-            if (int rc = rows_build_finish(rb.release())) return rc;
-            c.nodes_freed = true;
-            return (int)MBRWT_OK;
-        },
-        kNoLayoutHook);
-}
-
-static int sparse_columns_node_counts(const mbrwt_sparse_columns_desc &desc, const Tree &shape, int device,
-                                      uint64_t *counts) {
-    const uint64_t n = desc.num_rows;
-    const uint32_t D = (uint32_t)shape.nodes.size();
-    return node_counts_over(
-        shape, device, counts, []() { return (int)MBRWT_OK; },
-        [&](RowsFrom *rf, unsigned long long *d_counts, hipStream_t s) {
-            ColsRanges rg(desc);
-            for (uint64_t a = 0, b = 0; a < n; a = b) {
-                b = rg.cut(a, rows_range_rows(), 0);
-                LabelRows rows;
-                uint64_t L = 0;
-                if (int rc = cols_from_load(rf, rg.v, rg.cur, rg.ends, a, b, &rows, &L)) return rc;
-                if (int rc = rows_counts_range(rows, b - a, D, d_counts, s)) return rc;
-                MBRWT_HIP(hipStreamSynchronize(s));
-                rg.advance();
-            }
-            return (int)MBRWT_OK;
-        });
-}
-
 // Layouts ROWS and AUTO over many rows build ranged: beyond kAutoRangedRows
 // the whole node image and the records side by side may not fit (C3: 214 GB
 // of node image + 160 GB of records).  AUTO falls back to the per-node
@@ -705,6 +498,371 @@ static int rows_shape_tree(const mbrwt_shape_desc *shape, uint64_t m, uint32_t a
     return shape_tree(sd, m, tree);
 }
 
+// ---- the build front ends over a label source -----------------------------
+// Row records, per-node row counts and the tree shape straight from a
+// matrix's labels, given as CSR rows (rows_from.hip) or
+// as sparse columns (rows_from_cols.hip; §11d): no node image at all, so the
+// device holds the records plus ONE range's labels.  A source is what the
+// two forms differ in -- the host check of the description, how a range of
+// rows is cut and loaded, the greedy partitioner's front end and the words of
+// the messages; create_from_source, node_counts_from_source and
+// tree_shape_from_source below are everything else, once.
+struct RowsFromEnd {
+    void operator()(RowsFrom *rf) const { rows_from_end(rf); }
+};
+// what a range's labels may take: the free device memory less the 8 GiB
+// reserve of create_rows_ranged and `pending` (the bytes the build will still
+// allocate)
+static double range_budget(uint64_t pending) {
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    const double left = (double)free_b - 8.0 * (1ull << 30) - (double)pending;
+    return std::max(left, (double)free_b / 8) / 1.2;
+}
+using U32s = std::vector<uint32_t>;  // a shape's BFS array
+
+struct RowsSource {
+    using Desc = mbrwt_rows_desc;
+    static constexpr const char *kWords = "rows";
+    static constexpr const char *kCreate = "mbrwt_create_from_rows";
+    static constexpr const char *kCounts = "mbrwt_rows_node_counts";
+    static constexpr const char *kShape = "mbrwt_tree_shape_from_rows";
+    const Desc &d;
+    explicit RowsSource(const Desc &desc) : d(desc) {}
+    static int check(const Desc &desc) { return check_rows_desc(desc); }
+    // the counts pass has no device check of a row's length
+    int counts_precheck() const {
+        for (uint64_t r = 0; r < d.num_rows; ++r)
+            if (d.offsets[r + 1] - d.offsets[r] > 0x7FFFu) {
+                set_error("row record deeper than the build walker supports, or a row of more than 32,767 labels");
+                return MBRWT_ERR_UNSUPPORTED;
+            }
+        return MBRWT_OK;
+    }
+    // the range after a: the largest [a, a + k kRowsAlign), k kRowsAlign <= R,
+    // whose labels fit the budget and the device sort's item count; a fixed
+    // range size (MBRWT_BUILD_ROWS_RANGE) is taken as it is
+    uint64_t cut(uint64_t a, uint64_t R, uint64_t pending) {
+        const uint64_t n = d.num_rows, *off = d.offsets;
+        if (build_tuning().rows_range != 0) return std::min(n, a + R);
+        const double budget = range_budget(pending);
+        return cut_range_fit(n, a, R, kRowsAlign, [&](uint64_t e) {
+            const uint64_t L = off[e] - off[a];
+            return L <= kRowsFromMaxLabels && (double)rows_from_range_bytes(e - a, L) <= budget;
+        });
+    }
+    int build_range(RowsFrom *rf, RowsBuild *rb, uint64_t a, uint64_t b, uint64_t *relations) {
+        return rows_from_range(rf, rb, d.offsets, d.cols, a, b, relations);
+    }
+    int load(RowsFrom *rf, uint64_t a, uint64_t b, LabelRows *rows) {
+        return rows_from_load(rf, d.offsets, d.cols, a, b, rows);
+    }
+    void advance() {}
+    int greedy_shape(int device, U32s &nc, U32s &fc, U32s &lc) const {
+        return greedy_shape_from_rows(d, device, nc, fc, lc);
+    }
+};
+
+// One cursor per column walks the ranges; a range is cut from the cursors
+// (cols_host.hpp cut_cols_range: the labels of a candidate range by bisection
+// from every cursor) and its slices [cur, ends) end where the next range's begin.
+struct ColsSource {
+    using Desc = mbrwt_sparse_columns_desc;
+    static constexpr const char *kWords = "sparse columns";
+    static constexpr const char *kCreate = "mbrwt_create_from_sparse_columns";
+    static constexpr const char *kCounts = "mbrwt_sparse_columns_node_counts";
+    static constexpr const char *kShape = "mbrwt_tree_shape_from_sparse_columns";
+    ColsView v;
+    std::vector<uint64_t> cur, ends;
+    explicit ColsSource(const Desc &d) {
+        v.num_rows = d.num_rows;
+        v.num_columns = d.num_columns;
+        v.offsets = d.offsets;
+        v.rows = d.rows;
+        v.rows32 = d.rows32;
+    }
+    static int check(const Desc &desc) { return check_sparse_columns_desc(desc); }
+    int counts_precheck() const { return MBRWT_OK; }  // (cols_from_load checks every id and row)
+    uint64_t cut(uint64_t a, uint64_t R, uint64_t pending) {
+        if (a == 0) cur.assign(v.offsets, v.offsets + v.num_columns);  // the cursors start at the columns' heads
+        const bool fixed = build_tuning().rows_range != 0;
+        const uint64_t b = cut_cols_range(v.num_rows, v.num_columns, a, R, kRowsAlign, fixed,
+                                          fixed ? 0.0 : range_budget(pending),
+                                          [&](uint64_t e) { return cols_cut_slices(v, cur, e, nullptr); });
+        cols_cut_slices(v, cur, b, &ends);
+        return b;
+    }
+    int build_range(RowsFrom *rf, RowsBuild *rb, uint64_t a, uint64_t b, uint64_t *relations) {
+        return cols_from_range(rf, rb, v, cur, ends, a, b, relations);
+    }
+    int load(RowsFrom *rf, uint64_t a, uint64_t b, LabelRows *rows) {
+        uint64_t L = 0;
+        return cols_from_load(rf, v, cur, ends, a, b, rows, &L);
+    }
+    void advance() { cur.swap(ends); }
+    int greedy_shape(int device, U32s &nc, U32s &fc, U32s &lc) const {
+        return greedy_shape_from_sparse_columns(v, device, nc, fc, lc);
+    }
+};
+
+template <class Source>
+static int null_source_argument() {
+    set_error(std::string("null ") + Source::kWords + " description or output pointer");
+    return MBRWT_ERR_INVALID;
+}
+
+// mbrwt_create_from_rows / _sparse_columns.  Ranges are multiples of
+// kRowsAlign rows; the first (at most kRowsFirstRange rows) decides the record
+// code and layout; every range is cut so that its labels fit the memory left;
+// MBRWT_BUILD_ROWS_RANGE fixes the size.
+template <class Source>
+static int create_from_source(const typename Source::Desc *desc, const mbrwt_shape_desc *shape, uint32_t arity,
+                              int device, mbrwt_ctx **out) {
+    if (!desc || !out) return null_source_argument<Source>();
+    *out = nullptr;
+    return guarded(Source::kCreate, [&]() -> int {
+        const int layout = resolve_layout();
+        if (layout == LAYOUT_NODES || layout == LAYOUT_BOTH) {
+            set_error(std::string(Source::kCreate) + " builds row records only: layout AUTO or ROWS");
+            return MBRWT_ERR_UNSUPPORTED;
+        }
+        const uint64_t n = desc->num_rows, m = desc->num_columns;
+        if (n == 0 || m == 0) {  // the context of the same empty matrix from its (empty) dense columns
+            std::vector<const uint64_t *> none(m, nullptr);
+            const mbrwt_columns_desc cd{n, m, none.data(), shape ? 2u : arity};
+            return mbrwt_create_from_columns(&cd, device, out);
+        }
+        if (const int rc = Source::check(*desc)) return rc;
+        Tree tree;
+        if (const int rc = rows_shape_tree(shape, m, arity, tree)) return rc;
+        Source src(*desc);
+        return create_common(
+            device, out,
+            [&](Ctx &c) -> int {
+                c.tree = tree;
+                c.tree.num_rows = n;
+                RowsFrom *rfp = nullptr;
+                if (int rc = rows_from_begin(c.tree, c.stream, &rfp)) return rc;
+                std::unique_ptr<RowsFrom, RowsFromEnd> rf(rfp);
+                // (auto_layout = false: there is no node image to fall back to)
+                RowsBuildPtr rb(rows_build_begin(c, n, kRowsAlign, false));
+                if (!rb) return MBRWT_ERR_NOMEM;
+                const bool fixed = build_tuning().rows_range != 0;
+                for (uint64_t a = 0, b = 0; a < n; a = b) {
+                    b = src.cut(a, fixed || a ? rows_range_rows() : std::min(rows_range_rows(), kRowsFirstRange),
+                                fixed ? 0 : rows_build_pending_bytes(rb.get(), n - a));
+                    if (int rc = src.build_range(rf.get(), rb.get(), a, b, &c.tree.num_relations))
+                        return rc;  // (rb frees the build)
+                    src.advance();
+                }
+                rf.reset();
+                if (int rc = rows_build_finish(rb.release())) return rc;
+                c.nodes_freed = true;
+                return MBRWT_OK;
+            },
+            kNoLayoutHook);
+    });
+}
+
+// mbrwt_rows_node_counts / mbrwt_sparse_columns_node_counts: per-node row
+// counts under a tree shape (rows_counts.hip).  The ranges
+// and the loader of the build without any record, so a range takes the memory
+// the records would; the counts accumulate on the device across the ranges
+// and come back once, dnode u + 1 of the shape table being BFS node u.
+template <class Source>
+static int node_counts_from_source(const typename Source::Desc *desc, const mbrwt_shape_desc *shape, uint32_t arity,
+                                   int device, uint64_t *counts) {
+    if (!desc || !counts) return null_source_argument<Source>();
+    return guarded(Source::kCounts, [&]() -> int {
+        const uint64_t n = desc->num_rows, m = desc->num_columns;
+        if (m == 0) {  // no leaf: whatever nodes the caller's shape names see no row
+            if (shape) std::fill(counts, counts + shape->num_nodes, 0);
+            return MBRWT_OK;
+        }
+        if (n && Source::check(*desc)) return MBRWT_ERR_INVALID;
+        Tree tree;
+        if (const int rc = rows_shape_tree(shape, m, arity, tree)) return rc;
+        std::fill(counts, counts + tree.num_nodes, 0);
+        if (n == 0) return MBRWT_OK;
+        const size_t D = tree.nodes.size();
+        // the walk's limits (rows_emit.hpp emit_label_masks): internal levels on a path
+        std::vector<uint32_t> level(D, 0);
+        for (size_t v = 1; v < D; ++v) {
+            const DevNode &dn = tree.nodes[v];
+            if (dn.kind == KIND_LEAF) continue;
+            if (v == 1) level[v] = 1;
+            if (level[v] > kRowsMaxHeight) {
+                set_error(rows_limits_message());
+                return MBRWT_ERR_UNSUPPORTED;
+            }
+            for (uint32_t c = 0; c < dn.arity; ++c) level[dn.first_child + c] = level[v] + 1;
+        }
+        Source src(*desc);
+        if (int rc = src.counts_precheck()) return rc;
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+            set_error("no HIP device available");
+            return MBRWT_ERR_DEVICE;
+        }
+        if (device < 0 || device >= ndev) {
+            set_error("device index out of range");
+            return MBRWT_ERR_INVALID;
+        }
+        MBRWT_HIP(hipSetDevice(device));
+        struct Scope {
+            hipStream_t s = nullptr;
+            unsigned long long *d_counts = nullptr;
+            RowsFrom *rf = nullptr;
+            ~Scope() {
+                rows_from_end(rf);
+                if (d_counts) (void)hipFree(d_counts);
+                if (s) (void)hipStreamDestroy(s);
+            }
+        } sc;
+        MBRWT_HIP(hipStreamCreateWithFlags(&sc.s, hipStreamNonBlocking));
+        if (int rc = rows_from_begin(tree, sc.s, &sc.rf)) return rc;
+        MBRWT_HIP(hipMalloc(&sc.d_counts, D * sizeof(uint64_t)));
+        MBRWT_HIP(hipMemsetAsync(sc.d_counts, 0, D * sizeof(uint64_t), sc.s));
+        for (uint64_t a = 0, b = 0; a < n; a = b) {
+            b = src.cut(a, rows_range_rows(), 0);
+            LabelRows rows;
+            if (int rc = src.load(sc.rf, a, b, &rows)) return rc;
+            if (int rc = rows_counts_range(rows, b - a, (uint32_t)D, sc.d_counts, sc.s)) return rc;
+            // (the next load overwrites the range's buffers)
+            MBRWT_HIP(hipStreamSynchronize(sc.s));
+            src.advance();
+        }
+        std::vector<unsigned long long> h(D);
+        MBRWT_HIP(hipMemcpyAsync(h.data(), sc.d_counts, D * sizeof(uint64_t), hipMemcpyDeviceToHost, sc.s));
+        MBRWT_HIP(hipStreamSynchronize(sc.s));
+        for (size_t u = 0; u + 1 < D; ++u) counts[u] = h[u + 1];
+        return MBRWT_OK;
+    });
+}
+
+// mbrwt_tree_shape_from_rows / _sparse_columns: the partitioner's shape, then
+// the relax step over the counts of the whole counts entry point above (its
+// checks and zero-fill run again)
+template <class Source>
+static int tree_shape_from_source(const typename Source::Desc *desc, int partitioner, uint32_t arity,
+                                  uint64_t relax_max_arity, int device, mbrwt_tree **out) {
+    if (!desc || !out) return null_source_argument<Source>();
+    *out = nullptr;
+    if (partitioner != MBRWT_PARTITIONER_BASIC && partitioner != MBRWT_PARTITIONER_GREEDY) {
+        set_error("partitioner must be MBRWT_PARTITIONER_BASIC or MBRWT_PARTITIONER_GREEDY");
+        return MBRWT_ERR_INVALID;
+    }
+    return guarded(Source::kShape, [&]() -> int {
+        const uint64_t n = desc->num_rows, m = desc->num_columns;
+        std::vector<uint32_t> nc, fc, lc;
+        if (n && m && Source::check(*desc)) return MBRWT_ERR_INVALID;
+        if (partitioner == MBRWT_PARTITIONER_BASIC) {  // (reads no label: the counts pass checks them)
+            if (const int rc = basic_shape(m, arity, nc, fc, lc)) return rc;
+        } else {
+            if (const int rc = Source(*desc).greedy_shape(device, nc, fc, lc)) return rc;
+        }
+        if (relax_max_arity > 1 && nc.size() > 1) {
+            const mbrwt_shape_desc sd{(uint32_t)nc.size(), nc.data(), fc.data(), lc.data()};
+            std::vector<uint64_t> counts(nc.size(), 0);
+            if (const int rc = node_counts_from_source<Source>(desc, &sd, 0, device, counts.data())) return rc;
+            std::vector<uint32_t> rn, rf, rl;
+            if (const int rc = relax_shape(sd, counts.data(), relax_max_arity, rn, rf, rl)) return rc;
+            nc.swap(rn);
+            fc.swap(rf);
+            lc.swap(rl);
+        }
+        return shape_only_tree(m, std::move(nc), std::move(fc), std::move(lc), out);
+    });
+}
+
+// ---- the query entry points ------------------------------------------------
+// body(c, s) of the query `name` on ctx: under the context's lock, behind its
+// workspace fence, on its device and guarded.  stream: the caller's `void
+// *stream` argument of a device-buffer call (s = *stream), null for a
+// host-buffer call (s = the context's own stream).  rows16: the call writes
+// u16 labels, refused -- before any HIP call -- on a context too wide for them.
+template <class Body>
+static int query(mbrwt_ctx *ctx, void *const *stream, const char *name, Body &&body, bool rows16 = false) {
+    Ctx &c = *C(ctx);
+    const hipStream_t s = stream ? reinterpret_cast<hipStream_t>(*stream) : c.stream;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (rows16 && !rows16_supported(c)) return MBRWT_ERR_UNSUPPORTED;
+    WsFence fence_(c.fence, s);
+    return guarded(name, [&]() -> int {
+        MBRWT_HIP(hipSetDevice(c.device));
+        return body(c, s);
+    });
+}
+
+static int invalid_argument() {
+    set_error("invalid argument");
+    return MBRWT_ERR_INVALID;
+}
+
+// mbrwt_get_rows[16]*: the three calls once, on the label type (u32, or u16
+// on contexts of at most 65,536 columns)
+template <class Label>
+static int run_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, Label *d_cols, uint64_t cap,
+                    uint64_t *needed, hipStream_t s) {
+    if constexpr (sizeof(Label) == 2)
+        return run_get_rows16(c, d_rows, n, d_offsets, d_cols, cap, needed, s);
+    else
+        return run_get_rows(c, d_rows, n, d_offsets, d_cols, cap, needed, s);
+}
+
+template <class Label>
+static int get_rows_device(const char *name, mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets,
+                           Label *d_cols, uint64_t cols_cap, uint64_t *cols_needed, void *stream) {
+    if (!ctx || (n && (!d_rows || !d_offsets)) || (!n && !d_offsets)) return invalid_argument();
+    return query(ctx, &stream, name, [&](Ctx &c, hipStream_t s) {
+        return run_rows(c, d_rows, n, d_offsets, d_cols, d_cols ? cols_cap : 0, cols_needed, s);
+    }, sizeof(Label) == 2);
+}
+
+template <class Label>
+static int get_rows_device_async(const char *name, mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n,
+                                 uint64_t *d_offsets, Label *d_cols, uint64_t cols_cap, uint64_t *d_status,
+                                 void *stream) {
+    if (!ctx || !d_status || (n && (!d_rows || !d_offsets)) || (!n && !d_offsets)) return invalid_argument();
+    return query(ctx, &stream, name, [&](Ctx &c, hipStream_t s) -> int {
+        if (c.rows.ready && c.kernel_variant == 0 && n > 0)
+            return rows_get_rows(c, d_rows, n, d_offsets, d_cols, d_cols ? cols_cap : 0, nullptr, s, d_status,
+                                 sizeof(Label));
+        // other images: the synchronous call, then its status on the stream
+        uint64_t need = 0;
+        const int rc = run_rows(c, d_rows, n, d_offsets, d_cols, d_cols ? cols_cap : 0, &need, s);
+        if (rc != MBRWT_OK && rc != MBRWT_ERR_CAPACITY && rc != MBRWT_ERR_RANGE) return rc;
+        return rows_set_status(d_status, need, rc, s);
+    }, sizeof(Label) == 2);
+}
+
+template <class Label>
+static int get_rows_host(const char *name, mbrwt_ctx *ctx, const uint64_t *rows, uint64_t n, uint64_t *offsets,
+                         Label *cols, uint64_t cols_cap, uint64_t *cols_needed) {
+    if (!ctx || !offsets || (n && !rows)) return invalid_argument();
+    return query(ctx, nullptr, name, [&](Ctx &c, hipStream_t) {
+        // chunks of the batch pipelined over PCIe (hostpipe.cpp)
+        return host_get_rows(c, rows, n, offsets, cols, cols ? cols_cap : 0, cols_needed, sizeof(Label));
+    }, sizeof(Label) == 2);
+}
+
+// the host classify calls' input: rows | read offsets | label offsets, one
+// host-path workspace; the first two uploaded on the context's stream
+struct ClassifyStage {
+    uint64_t *rows, *read_offsets, *label_offsets;
+};
+static int stage_classify(Ctx &c, const uint64_t *rows, uint64_t n_rows, const uint64_t *read_offsets,
+                          uint64_t n_reads, ClassifyStage &d) {
+    if (const int rc = ensure(c.ws_rows, (n_rows + 2 * (n_reads + 1)) * sizeof(uint64_t))) return rc;
+    d.rows = reinterpret_cast<uint64_t *>(c.ws_rows.buf);
+    d.read_offsets = d.rows + n_rows;
+    d.label_offsets = d.read_offsets + n_reads + 1;
+    if (n_rows) MBRWT_HIP(hipMemcpyAsync(d.rows, rows, n_rows * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
+    MBRWT_HIP(hipMemcpyAsync(d.read_offsets, read_offsets, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice,
+                             c.stream));
+    return MBRWT_OK;
+}
+
 }  // namespace mbrwt
 
 using namespace mbrwt;
@@ -716,7 +874,7 @@ int mbrwt_create(const mbrwt_tree_desc *desc, int device, mbrwt_ctx **out) {
         set_error("null tree description");
         return MBRWT_ERR_INVALID;
     }
-    try {
+    return guarded("mbrwt_create", [&]() -> int {
         int layout = resolve_layout();
         if (ranged_rows(layout, desc->num_rows) && desc->num_nodes) {
             const int rc = create_rows_ranged(device, desc->num_rows, desc->num_columns, out, layout,
@@ -740,13 +898,7 @@ int mbrwt_create(const mbrwt_tree_desc *desc, int device, mbrwt_ctx **out) {
                 layout);
         }
         return create_common(device, out, [&](Ctx &c) { return build_from_desc(*desc, device, c.tree); }, layout);
-    } catch (const std::bad_alloc &) {
-        set_error("host allocation failed");
-        return MBRWT_ERR_NOMEM;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_create");
-        return MBRWT_ERR_INVALID;
-    }
+    });
 }
 
 int mbrwt_create_synthetic_shaped(const mbrwt_synth_desc *desc, const mbrwt_shape_desc *shape, int device,
@@ -755,15 +907,7 @@ int mbrwt_create_synthetic_shaped(const mbrwt_synth_desc *desc, const mbrwt_shap
         set_error("null synthetic or shape description");
         return MBRWT_ERR_INVALID;
     }
-    try {
-        return create_synthetic_any(*desc, shape, device, out);
-    } catch (const std::bad_alloc &) {
-        set_error("host allocation failed");
-        return MBRWT_ERR_NOMEM;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_create_synthetic_shaped");
-        return MBRWT_ERR_INVALID;
-    }
+    return guarded("mbrwt_create_synthetic_shaped", [&] { return create_synthetic_any(*desc, shape, device, out); });
 }
 
 int mbrwt_create_synthetic(const mbrwt_synth_desc *desc, int device, mbrwt_ctx **out) {
@@ -771,15 +915,7 @@ int mbrwt_create_synthetic(const mbrwt_synth_desc *desc, int device, mbrwt_ctx *
         set_error("null synthetic description");
         return MBRWT_ERR_INVALID;
     }
-    try {
-        return create_synthetic_any(*desc, nullptr, device, out);
-    } catch (const std::bad_alloc &) {
-        set_error("host allocation failed");
-        return MBRWT_ERR_NOMEM;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_create_synthetic");
-        return MBRWT_ERR_INVALID;
-    }
+    return guarded("mbrwt_create_synthetic", [&] { return create_synthetic_any(*desc, nullptr, device, out); });
 }
 
 // rows >= 2^32 (Row = uint64_t, binary_matrix.hpp:11): the device builders
@@ -805,79 +941,24 @@ int mbrwt_create_from_columns(const mbrwt_columns_desc *desc, int device, mbrwt_
         set_error("null columns description");
         return MBRWT_ERR_INVALID;
     }
-    try {
+    return guarded("mbrwt_create_from_columns", [&]() -> int {
         if (desc->num_rows > kMaxRows)
             return create_via_desc(device, out, [&](hipStream_t s, const DescSink &emit) {
                 return desc_from_columns(*desc, device, s, 0, emit);
             });
         return create_common(device, out,
                              [&](Ctx &c) { return build_from_columns(*desc, device, c.tree, c.stream); });
-    } catch (const std::bad_alloc &) {
-        set_error("host allocation failed");
-        return MBRWT_ERR_NOMEM;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_create_from_columns");
-        return MBRWT_ERR_INVALID;
-    }
+    });
 }
 
 int mbrwt_create_from_rows(const mbrwt_rows_desc *desc, const mbrwt_shape_desc *shape, uint32_t arity, int device,
                            mbrwt_ctx **out) {
-    if (!desc || !out) {
-        set_error("null rows description or output pointer");
-        return MBRWT_ERR_INVALID;
-    }
-    *out = nullptr;
-    try {
-        const int layout = resolve_layout();
-        if (layout == LAYOUT_NODES || layout == LAYOUT_BOTH) {
-            set_error("mbrwt_create_from_rows builds row records only: layout AUTO or ROWS");
-            return MBRWT_ERR_UNSUPPORTED;
-        }
-        const uint64_t n = desc->num_rows, m = desc->num_columns;
-        if (n == 0 || m == 0) {  // the context of the same empty matrix from its (empty) columns
-            std::vector<const uint64_t *> none(m, nullptr);
-            const mbrwt_columns_desc cd{n, m, none.data(), shape ? 2u : arity};
-            return mbrwt_create_from_columns(&cd, device, out);
-        }
-        if (const int rc = check_rows_desc(*desc)) return rc;
-        Tree tree;
-        if (const int rc = rows_shape_tree(shape, m, arity, tree)) return rc;
-        return create_from_rows(*desc, tree, device, out);
-    } catch (const std::bad_alloc &) {
-        set_error("host allocation failed");
-        return MBRWT_ERR_NOMEM;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_create_from_rows");
-        return MBRWT_ERR_INVALID;
-    }
+    return create_from_source<RowsSource>(desc, shape, arity, device, out);
 }
 
 int mbrwt_rows_node_counts(const mbrwt_rows_desc *desc, const mbrwt_shape_desc *shape, uint32_t arity, int device,
                            uint64_t *counts) {
-    if (!desc || !counts) {
-        set_error("null rows description or output pointer");
-        return MBRWT_ERR_INVALID;
-    }
-    try {
-        const uint64_t n = desc->num_rows, m = desc->num_columns;
-        if (m == 0) {  // no leaf: whatever nodes the caller's shape names see no row
-            if (shape) std::fill(counts, counts + shape->num_nodes, 0);
-            return MBRWT_OK;
-        }
-        if (n && check_rows_desc(*desc)) return MBRWT_ERR_INVALID;
-        Tree tree;
-        if (const int rc = rows_shape_tree(shape, m, arity, tree)) return rc;
-        std::fill(counts, counts + tree.num_nodes, 0);
-        if (n == 0) return MBRWT_OK;
-        return rows_node_counts(*desc, tree, device, counts);
-    } catch (const std::bad_alloc &) {
-        set_error("host allocation failed");
-        return MBRWT_ERR_NOMEM;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_rows_node_counts");
-        return MBRWT_ERR_INVALID;
-    }
+    return node_counts_from_source<RowsSource>(desc, shape, arity, device, counts);
 }
 
 int mbrwt_tree_relax_shape(const mbrwt_shape_desc *shape, const uint64_t *counts, uint64_t max_arity,
@@ -887,158 +968,33 @@ int mbrwt_tree_relax_shape(const mbrwt_shape_desc *shape, const uint64_t *counts
         return MBRWT_ERR_INVALID;
     }
     *out = nullptr;
-    try {
+    return guarded("mbrwt_tree_relax_shape", [&]() -> int {
         std::vector<uint32_t> nc, fc, lc;
         if (const int rc = relax_shape(*shape, counts, max_arity, nc, fc, lc)) return rc;
         uint64_t m = 0;
         for (const uint32_t k : nc) m += k == 0;
         return shape_only_tree(m, std::move(nc), std::move(fc), std::move(lc), out);
-    } catch (const std::bad_alloc &) {
-        set_error("host allocation failed");
-        return MBRWT_ERR_NOMEM;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_tree_relax_shape");
-        return MBRWT_ERR_INVALID;
-    }
+    });
 }
 
 int mbrwt_tree_shape_from_rows(const mbrwt_rows_desc *desc, int partitioner, uint32_t arity, uint64_t relax_max_arity,
                                int device, mbrwt_tree **out) {
-    if (!desc || !out) {
-        set_error("null rows description or output pointer");
-        return MBRWT_ERR_INVALID;
-    }
-    *out = nullptr;
-    if (partitioner != MBRWT_PARTITIONER_BASIC && partitioner != MBRWT_PARTITIONER_GREEDY) {
-        set_error("partitioner must be MBRWT_PARTITIONER_BASIC or MBRWT_PARTITIONER_GREEDY");
-        return MBRWT_ERR_INVALID;
-    }
-    try {
-        const uint64_t n = desc->num_rows, m = desc->num_columns;
-        std::vector<uint32_t> nc, fc, lc;
-        if (n && m && check_rows_desc(*desc)) return MBRWT_ERR_INVALID;
-        if (partitioner == MBRWT_PARTITIONER_BASIC) {  // (reads no row: the labels are checked by the counts pass)
-            if (const int rc = basic_shape(m, arity, nc, fc, lc)) return rc;
-        } else {
-            if (const int rc = greedy_shape_from_rows(*desc, device, nc, fc, lc)) return rc;
-        }
-        if (relax_max_arity > 1 && nc.size() > 1) {
-            const mbrwt_shape_desc sd{(uint32_t)nc.size(), nc.data(), fc.data(), lc.data()};
-            std::vector<uint64_t> counts(nc.size(), 0);
-            if (const int rc = mbrwt_rows_node_counts(desc, &sd, 0, device, counts.data())) return rc;
-            std::vector<uint32_t> rn, rf, rl;
-            if (const int rc = relax_shape(sd, counts.data(), relax_max_arity, rn, rf, rl)) return rc;
-            nc.swap(rn);
-            fc.swap(rf);
-            lc.swap(rl);
-        }
-        return shape_only_tree(m, std::move(nc), std::move(fc), std::move(lc), out);
-    } catch (const std::bad_alloc &) {
-        set_error("host allocation failed");
-        return MBRWT_ERR_NOMEM;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_tree_shape_from_rows");
-        return MBRWT_ERR_INVALID;
-    }
+    return tree_shape_from_source<RowsSource>(desc, partitioner, arity, relax_max_arity, device, out);
 }
 
 int mbrwt_create_from_sparse_columns(const mbrwt_sparse_columns_desc *desc, const mbrwt_shape_desc *shape,
                                      uint32_t arity, int device, mbrwt_ctx **out) {
-    if (!desc || !out) {
-        set_error("null sparse columns description or output pointer");
-        return MBRWT_ERR_INVALID;
-    }
-    *out = nullptr;
-    try {
-        const int layout = resolve_layout();
-        if (layout == LAYOUT_NODES || layout == LAYOUT_BOTH) {
-            set_error("mbrwt_create_from_sparse_columns builds row records only: layout AUTO or ROWS");
-            return MBRWT_ERR_UNSUPPORTED;
-        }
-        const uint64_t n = desc->num_rows, m = desc->num_columns;
-        if (n == 0 || m == 0) {  // the context of the same empty matrix from its (empty) dense columns
-            std::vector<const uint64_t *> none(m, nullptr);
-            const mbrwt_columns_desc cd{n, m, none.data(), shape ? 2u : arity};
-            return mbrwt_create_from_columns(&cd, device, out);
-        }
-        if (const int rc = check_sparse_columns_desc(*desc)) return rc;
-        Tree tree;
-        if (const int rc = rows_shape_tree(shape, m, arity, tree)) return rc;
-        return create_from_sparse_columns(*desc, tree, device, out);
-    } catch (const std::bad_alloc &) {
-        set_error("host allocation failed");
-        return MBRWT_ERR_NOMEM;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_create_from_sparse_columns");
-        return MBRWT_ERR_INVALID;
-    }
+    return create_from_source<ColsSource>(desc, shape, arity, device, out);
 }
 
 int mbrwt_sparse_columns_node_counts(const mbrwt_sparse_columns_desc *desc, const mbrwt_shape_desc *shape,
                                      uint32_t arity, int device, uint64_t *counts) {
-    if (!desc || !counts) {
-        set_error("null sparse columns description or output pointer");
-        return MBRWT_ERR_INVALID;
-    }
-    try {
-        const uint64_t n = desc->num_rows, m = desc->num_columns;
-        if (m == 0) {  // no leaf: whatever nodes the caller's shape names see no row
-            if (shape) std::fill(counts, counts + shape->num_nodes, 0);
-            return MBRWT_OK;
-        }
-        if (n && check_sparse_columns_desc(*desc)) return MBRWT_ERR_INVALID;
-        Tree tree;
-        if (const int rc = rows_shape_tree(shape, m, arity, tree)) return rc;
-        std::fill(counts, counts + tree.num_nodes, 0);
-        if (n == 0) return MBRWT_OK;
-        return sparse_columns_node_counts(*desc, tree, device, counts);
-    } catch (const std::bad_alloc &) {
-        set_error("host allocation failed");
-        return MBRWT_ERR_NOMEM;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_sparse_columns_node_counts");
-        return MBRWT_ERR_INVALID;
-    }
+    return node_counts_from_source<ColsSource>(desc, shape, arity, device, counts);
 }
 
 int mbrwt_tree_shape_from_sparse_columns(const mbrwt_sparse_columns_desc *desc, int partitioner, uint32_t arity,
                                          uint64_t relax_max_arity, int device, mbrwt_tree **out) {
-    if (!desc || !out) {
-        set_error("null sparse columns description or output pointer");
-        return MBRWT_ERR_INVALID;
-    }
-    *out = nullptr;
-    if (partitioner != MBRWT_PARTITIONER_BASIC && partitioner != MBRWT_PARTITIONER_GREEDY) {
-        set_error("partitioner must be MBRWT_PARTITIONER_BASIC or MBRWT_PARTITIONER_GREEDY");
-        return MBRWT_ERR_INVALID;
-    }
-    try {
-        const uint64_t n = desc->num_rows, m = desc->num_columns;
-        std::vector<uint32_t> nc, fc, lc;
-        if (n && m && check_sparse_columns_desc(*desc)) return MBRWT_ERR_INVALID;
-        if (partitioner == MBRWT_PARTITIONER_BASIC) {  // (reads no id: the counts pass checks them)
-            if (const int rc = basic_shape(m, arity, nc, fc, lc)) return rc;
-        } else {
-            if (const int rc = greedy_shape_from_sparse_columns(cols_view(*desc), device, nc, fc, lc)) return rc;
-        }
-        if (relax_max_arity > 1 && nc.size() > 1) {
-            const mbrwt_shape_desc sd{(uint32_t)nc.size(), nc.data(), fc.data(), lc.data()};
-            std::vector<uint64_t> counts(nc.size(), 0);
-            if (const int rc = mbrwt_sparse_columns_node_counts(desc, &sd, 0, device, counts.data())) return rc;
-            std::vector<uint32_t> rn, rf, rl;
-            if (const int rc = relax_shape(sd, counts.data(), relax_max_arity, rn, rf, rl)) return rc;
-            nc.swap(rn);
-            fc.swap(rf);
-            lc.swap(rl);
-        }
-        return shape_only_tree(m, std::move(nc), std::move(fc), std::move(lc), out);
-    } catch (const std::bad_alloc &) {
-        set_error("host allocation failed");
-        return MBRWT_ERR_NOMEM;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_tree_shape_from_sparse_columns");
-        return MBRWT_ERR_INVALID;
-    }
+    return tree_shape_from_source<ColsSource>(desc, partitioner, arity, relax_max_arity, device, out);
 }
 
 int mbrwt_create_from_columns_relaxed(const mbrwt_columns_desc *desc, uint64_t relax_max_arity, int device,
@@ -1047,7 +1003,7 @@ int mbrwt_create_from_columns_relaxed(const mbrwt_columns_desc *desc, uint64_t r
         set_error("null columns description");
         return MBRWT_ERR_INVALID;
     }
-    try {
+    return guarded("mbrwt_create_from_columns_relaxed", [&]() -> int {
         if (desc->num_rows > kMaxRows)
             return create_via_desc(device, out, [&](hipStream_t s, const DescSink &emit) {
                 return desc_from_columns(*desc, device, s, relax_max_arity, emit);
@@ -1055,13 +1011,7 @@ int mbrwt_create_from_columns_relaxed(const mbrwt_columns_desc *desc, uint64_t r
         return create_common(device, out, [&](Ctx &c) {
             return build_from_columns(*desc, device, c.tree, c.stream, relax_max_arity);
         });
-    } catch (const std::bad_alloc &) {
-        set_error("host allocation failed");
-        return MBRWT_ERR_NOMEM;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_create_from_columns_relaxed");
-        return MBRWT_ERR_INVALID;
-    }
+    });
 }
 
 int mbrwt_create_relaxed(const mbrwt_tree_desc *desc, uint64_t max_arity, int device, mbrwt_ctx **out) {
@@ -1069,7 +1019,7 @@ int mbrwt_create_relaxed(const mbrwt_tree_desc *desc, uint64_t max_arity, int de
         set_error("null tree description");
         return MBRWT_ERR_INVALID;
     }
-    try {
+    return guarded("mbrwt_create_relaxed", [&]() -> int {
         if (desc->num_rows > kMaxRows)
             return create_via_desc(device, out, [&](hipStream_t s, const DescSink &emit) {
                 return relaxed_desc(*desc, max_arity, device, s, emit);
@@ -1077,13 +1027,7 @@ int mbrwt_create_relaxed(const mbrwt_tree_desc *desc, uint64_t max_arity, int de
         return create_common(device, out, [&](Ctx &c) {
             return build_relaxed_from_desc(*desc, max_arity, device, c.tree, c.stream);
         });
-    } catch (const std::bad_alloc &) {
-        set_error("host allocation failed");
-        return MBRWT_ERR_NOMEM;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_create_relaxed");
-        return MBRWT_ERR_INVALID;
-    }
+    });
 }
 
 void mbrwt_destroy(mbrwt_ctx *ctx) { release(C(ctx)); }
@@ -1093,10 +1037,13 @@ int mbrwt_ctx_clone(mbrwt_ctx *src, mbrwt_ctx **out) {
         set_error("null context or output pointer");
         return MBRWT_ERR_INVALID;
     }
-    Ctx *c = nullptr;
-    const int rc = clone_ctx(C(src), &c);
-    *out = reinterpret_cast<mbrwt_ctx *>(c);
-    return rc;
+    *out = nullptr;
+    return guarded("mbrwt_ctx_clone", [&] {
+        Ctx *c = nullptr;
+        const int rc = clone_ctx(C(src), &c);
+        *out = reinterpret_cast<mbrwt_ctx *>(c);
+        return rc;
+    });
 }
 
 uint64_t mbrwt_num_rows(const mbrwt_ctx *ctx) { return ctx ? C(ctx)->tree.num_rows : 0; }
@@ -1234,335 +1181,148 @@ uint64_t mbrwt_num_shards(const mbrwt_ctx *ctx) { return ctx ? std::max<uint64_t
 
 int mbrwt_get_rows_device(mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, uint32_t *d_cols,
                           uint64_t cols_cap, uint64_t *cols_needed, void *stream) {
-    if (!ctx || (n && (!d_rows || !d_offsets)) || (!n && !d_offsets)) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    std::lock_guard<std::mutex> lk(c.mu);
-    WsFence fence_(c.fence, reinterpret_cast<hipStream_t>(stream));
-    try {
-        if (hipSetDevice(c.device) != hipSuccess) return hip_fail(hipGetLastError(), "hipSetDevice");
-        return run_get_rows(c, d_rows, n, d_offsets, d_cols, d_cols ? cols_cap : 0, cols_needed,
-                            reinterpret_cast<hipStream_t>(stream));
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_get_rows_device");
-        return MBRWT_ERR_INVALID;
-    }
+    return get_rows_device("mbrwt_get_rows_device", ctx, d_rows, n, d_offsets, d_cols, cols_cap, cols_needed, stream);
 }
 
 int mbrwt_get_rows_device_async(mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets,
                                 uint32_t *d_cols, uint64_t cols_cap, uint64_t *d_status, void *stream) {
-    if (!ctx || !d_status || (n && (!d_rows || !d_offsets)) || (!n && !d_offsets)) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    std::lock_guard<std::mutex> lk(c.mu);
-    WsFence fence_(c.fence, s);
-    try {
-        if (hipSetDevice(c.device) != hipSuccess) return hip_fail(hipGetLastError(), "hipSetDevice");
-        if (c.rows.ready && c.kernel_variant == 0 && n > 0)
-            return rows_get_rows(c, d_rows, n, d_offsets, d_cols, d_cols ? cols_cap : 0, nullptr, s, d_status);
-        // other images: the synchronous call, then its status on the stream
-        uint64_t need = 0;
-        const int rc = run_get_rows(c, d_rows, n, d_offsets, d_cols, d_cols ? cols_cap : 0, &need, s);
-        if (rc != MBRWT_OK && rc != MBRWT_ERR_CAPACITY && rc != MBRWT_ERR_RANGE) return rc;
-        return rows_set_status(d_status, need, rc, s);
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_get_rows_device_async");
-        return MBRWT_ERR_INVALID;
-    }
+    return get_rows_device_async("mbrwt_get_rows_device_async", ctx, d_rows, n, d_offsets, d_cols, cols_cap, d_status,
+                                 stream);
 }
 
 int mbrwt_get_rows(mbrwt_ctx *ctx, const uint64_t *rows, uint64_t n, uint64_t *offsets, uint32_t *cols,
                    uint64_t cols_cap, uint64_t *cols_needed) {
-    if (!ctx || !offsets || (n && !rows)) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    std::lock_guard<std::mutex> lk(c.mu);
-    WsFence fence_(c.fence, c.stream);
-    try {
-        MBRWT_HIP(hipSetDevice(c.device));
-        // chunks of the batch pipelined over PCIe (hostpipe.cpp)
-        return host_get_rows(c, rows, n, offsets, cols, cols ? cols_cap : 0, cols_needed);
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_get_rows");
-        return MBRWT_ERR_INVALID;
-    }
+    return get_rows_host("mbrwt_get_rows", ctx, rows, n, offsets, cols, cols_cap, cols_needed);
 }
 
 // u16 labels: the three calls above with a narrow `cols` (contexts of at most 65,536 columns)
 int mbrwt_get_rows16_device(mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, uint16_t *d_cols,
                             uint64_t cols_cap, uint64_t *cols_needed, void *stream) {
-    if (!ctx || (n && (!d_rows || !d_offsets)) || (!n && !d_offsets)) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    std::lock_guard<std::mutex> lk(c.mu);
-    if (!rows16_supported(c)) return MBRWT_ERR_UNSUPPORTED;
-    WsFence fence_(c.fence, reinterpret_cast<hipStream_t>(stream));
-    try {
-        if (hipSetDevice(c.device) != hipSuccess) return hip_fail(hipGetLastError(), "hipSetDevice");
-        return run_get_rows16(c, d_rows, n, d_offsets, d_cols, d_cols ? cols_cap : 0, cols_needed,
-                              reinterpret_cast<hipStream_t>(stream));
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_get_rows16_device");
-        return MBRWT_ERR_INVALID;
-    }
+    return get_rows_device("mbrwt_get_rows16_device", ctx, d_rows, n, d_offsets, d_cols, cols_cap, cols_needed, stream);
 }
 
 int mbrwt_get_rows16_device_async(mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets,
                                   uint16_t *d_cols, uint64_t cols_cap, uint64_t *d_status, void *stream) {
-    if (!ctx || !d_status || (n && (!d_rows || !d_offsets)) || (!n && !d_offsets)) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    std::lock_guard<std::mutex> lk(c.mu);
-    if (!rows16_supported(c)) return MBRWT_ERR_UNSUPPORTED;
-    WsFence fence_(c.fence, s);
-    try {
-        if (hipSetDevice(c.device) != hipSuccess) return hip_fail(hipGetLastError(), "hipSetDevice");
-        if (c.rows.ready && c.kernel_variant == 0 && n > 0)
-            return rows_get_rows(c, d_rows, n, d_offsets, d_cols, d_cols ? cols_cap : 0, nullptr, s, d_status, 2);
-        // other images: the synchronous call, then its status on the stream
-        uint64_t need = 0;
-        const int rc = run_get_rows16(c, d_rows, n, d_offsets, d_cols, d_cols ? cols_cap : 0, &need, s);
-        if (rc != MBRWT_OK && rc != MBRWT_ERR_CAPACITY && rc != MBRWT_ERR_RANGE) return rc;
-        return rows_set_status(d_status, need, rc, s);
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_get_rows16_device_async");
-        return MBRWT_ERR_INVALID;
-    }
+    return get_rows_device_async("mbrwt_get_rows16_device_async", ctx, d_rows, n, d_offsets, d_cols, cols_cap,
+                                 d_status, stream);
 }
 
 int mbrwt_get_rows16(mbrwt_ctx *ctx, const uint64_t *rows, uint64_t n, uint64_t *offsets, uint16_t *cols,
                      uint64_t cols_cap, uint64_t *cols_needed) {
-    if (!ctx || !offsets || (n && !rows)) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    std::lock_guard<std::mutex> lk(c.mu);
-    if (!rows16_supported(c)) return MBRWT_ERR_UNSUPPORTED;
-    WsFence fence_(c.fence, c.stream);
-    try {
-        MBRWT_HIP(hipSetDevice(c.device));
-        return host_get_rows(c, rows, n, offsets, cols, cols ? cols_cap : 0, cols_needed, 2);
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_get_rows16");
-        return MBRWT_ERR_INVALID;
-    }
+    return get_rows_host("mbrwt_get_rows16", ctx, rows, n, offsets, cols, cols_cap, cols_needed);
 }
 
 int mbrwt_get_column_device(mbrwt_ctx *ctx, uint64_t column, uint64_t *d_rows, uint64_t rows_cap,
                             uint64_t *rows_needed, void *stream) {
-    if (!ctx) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    std::lock_guard<std::mutex> lk(c.mu);
-    WsFence fence_(c.fence, reinterpret_cast<hipStream_t>(stream));
-    try {
-        MBRWT_HIP(hipSetDevice(c.device));
-        return run_get_column(c, column, d_rows, d_rows ? rows_cap : 0, rows_needed,
-                              reinterpret_cast<hipStream_t>(stream));
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_get_column_device");
-        return MBRWT_ERR_INVALID;
-    }
+    if (!ctx) return invalid_argument();
+    return query(ctx, &stream, "mbrwt_get_column_device", [&](Ctx &c, hipStream_t s) {
+        return run_get_column(c, column, d_rows, d_rows ? rows_cap : 0, rows_needed, s);
+    });
 }
 
 int mbrwt_get_column(mbrwt_ctx *ctx, uint64_t column, uint64_t *rows, uint64_t rows_cap, uint64_t *rows_needed) {
-    if (!ctx) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    std::lock_guard<std::mutex> lk(c.mu);
-    WsFence fence_(c.fence, c.stream);
-    try {
-        MBRWT_HIP(hipSetDevice(c.device));
+    if (!ctx) return invalid_argument();
+    return query(ctx, nullptr, "mbrwt_get_column", [&](Ctx &c, hipStream_t s) -> int {
         int rc;
         uint64_t needed = 0;
         // the column's size is known after the first (counting) phase
         if ((rc = ensure(c.ws_out, std::max<uint64_t>(rows_cap, 1) * sizeof(uint64_t)))) return rc;
-        rc = run_get_column(c, column, reinterpret_cast<uint64_t *>(c.ws_out.buf), rows ? rows_cap : 0, &needed,
-                            c.stream);
+        rc = run_get_column(c, column, reinterpret_cast<uint64_t *>(c.ws_out.buf), rows ? rows_cap : 0, &needed, s);
         if (rows_needed) *rows_needed = needed;
         if (rc) return rc;
-        if (needed)
-            MBRWT_HIP(hipMemcpyAsync(rows, c.ws_out.buf, needed * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream));
-        MBRWT_HIP(hipStreamSynchronize(c.stream));
+        if (needed) MBRWT_HIP(hipMemcpyAsync(rows, c.ws_out.buf, needed * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        MBRWT_HIP(hipStreamSynchronize(s));
         return MBRWT_OK;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_get_column");
-        return MBRWT_ERR_INVALID;
-    }
+    });
 }
 
 int mbrwt_get_batch_device(mbrwt_ctx *ctx, const uint64_t *d_rows, const uint64_t *d_cols, uint64_t n,
                            uint8_t *d_out, void *stream) {
-    if (!ctx || (n && (!d_rows || !d_cols || !d_out))) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    std::lock_guard<std::mutex> lk(c.mu);
-    WsFence fence_(c.fence, reinterpret_cast<hipStream_t>(stream));
-    MBRWT_HIP(hipSetDevice(c.device));
-    return run_get_batch(c, d_rows, d_cols, n, d_out, reinterpret_cast<hipStream_t>(stream));
+    if (!ctx || (n && (!d_rows || !d_cols || !d_out))) return invalid_argument();
+    return query(ctx, &stream, "mbrwt_get_batch_device",
+                 [&](Ctx &c, hipStream_t s) { return run_get_batch(c, d_rows, d_cols, n, d_out, s); });
 }
 
 int mbrwt_get_batch(mbrwt_ctx *ctx, const uint64_t *rows, const uint64_t *cols, uint64_t n, uint8_t *out) {
-    if (!ctx || (n && (!rows || !cols || !out))) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    std::lock_guard<std::mutex> lk(c.mu);
-    WsFence fence_(c.fence, c.stream);
-    MBRWT_HIP(hipSetDevice(c.device));
-    if (!n) return MBRWT_OK;
-    int rc;
-    if ((rc = ensure(c.ws_rows, n * sizeof(uint64_t) * 2 + n))) return rc;
-    uint64_t *d_r = reinterpret_cast<uint64_t *>(c.ws_rows.buf);
-    uint64_t *d_c = d_r + n;
-    uint8_t *d_o = reinterpret_cast<uint8_t *>(d_c + n);
-    MBRWT_HIP(hipMemcpyAsync(d_r, rows, n * 8, hipMemcpyHostToDevice, c.stream));
-    MBRWT_HIP(hipMemcpyAsync(d_c, cols, n * 8, hipMemcpyHostToDevice, c.stream));
-    rc = run_get_batch(c, d_r, d_c, n, d_o, c.stream);
-    if (rc) return rc;
-    MBRWT_HIP(hipMemcpyAsync(out, d_o, n, hipMemcpyDeviceToHost, c.stream));
-    MBRWT_HIP(hipStreamSynchronize(c.stream));
-    return MBRWT_OK;
+    if (!ctx || (n && (!rows || !cols || !out))) return invalid_argument();
+    return query(ctx, nullptr, "mbrwt_get_batch", [&](Ctx &c, hipStream_t s) -> int {
+        if (!n) return MBRWT_OK;
+        int rc;
+        if ((rc = ensure(c.ws_rows, n * sizeof(uint64_t) * 2 + n))) return rc;
+        uint64_t *d_r = reinterpret_cast<uint64_t *>(c.ws_rows.buf);
+        uint64_t *d_c = d_r + n;
+        uint8_t *d_o = reinterpret_cast<uint8_t *>(d_c + n);
+        MBRWT_HIP(hipMemcpyAsync(d_r, rows, n * 8, hipMemcpyHostToDevice, s));
+        MBRWT_HIP(hipMemcpyAsync(d_c, cols, n * 8, hipMemcpyHostToDevice, s));
+        rc = run_get_batch(c, d_r, d_c, n, d_o, s);
+        if (rc) return rc;
+        MBRWT_HIP(hipMemcpyAsync(out, d_o, n, hipMemcpyDeviceToHost, s));
+        MBRWT_HIP(hipStreamSynchronize(s));
+        return MBRWT_OK;
+    });
 }
 
 int mbrwt_count_labels_device(mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n, uint64_t *d_counts,
                               void *stream) {
-    if (!ctx || (n && !d_rows) || !d_counts) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    std::lock_guard<std::mutex> lk(c.mu);
-    WsFence fence_(c.fence, reinterpret_cast<hipStream_t>(stream));
-    MBRWT_HIP(hipSetDevice(c.device));
-    return run_count_labels(c, d_rows, n, d_counts, reinterpret_cast<hipStream_t>(stream));
+    if (!ctx || (n && !d_rows) || !d_counts) return invalid_argument();
+    return query(ctx, &stream, "mbrwt_count_labels_device",
+                 [&](Ctx &c, hipStream_t s) { return run_count_labels(c, d_rows, n, d_counts, s); });
 }
 
 int mbrwt_get_labels_batch_device(mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n_rows,
                                   const uint64_t *d_read_offsets, uint64_t n_reads, double presence_ratio,
                                   uint64_t *d_label_offsets, uint32_t *d_labels, uint64_t labels_cap,
                                   uint64_t *labels_needed, void *stream) {
-    if (!ctx || (n_rows && !d_rows) || !d_read_offsets || !d_label_offsets) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    std::lock_guard<std::mutex> lk(c.mu);
-    WsFence fence_(c.fence, reinterpret_cast<hipStream_t>(stream));
-    try {
-        MBRWT_HIP(hipSetDevice(c.device));
+    if (!ctx || (n_rows && !d_rows) || !d_read_offsets || !d_label_offsets) return invalid_argument();
+    return query(ctx, &stream, "mbrwt_get_labels_batch_device", [&](Ctx &c, hipStream_t s) {
         return run_get_labels_batch(c, d_rows, n_rows, d_read_offsets, n_reads, presence_ratio, d_label_offsets,
-                                    d_labels, d_labels ? labels_cap : 0, labels_needed,
-                                    reinterpret_cast<hipStream_t>(stream));
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_get_labels_batch_device");
-        return MBRWT_ERR_INVALID;
-    }
+                                    d_labels, d_labels ? labels_cap : 0, labels_needed, s);
+    });
 }
 
 int mbrwt_get_labels_batch(mbrwt_ctx *ctx, const uint64_t *rows, uint64_t n_rows, const uint64_t *read_offsets,
                            uint64_t n_reads, double presence_ratio, uint64_t *label_offsets, uint32_t *labels,
                            uint64_t labels_cap, uint64_t *labels_needed) {
-    if (!ctx || (n_rows && !rows) || !read_offsets || !label_offsets) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    std::lock_guard<std::mutex> lk(c.mu);
-    WsFence fence_(c.fence, c.stream);
-    try {
-        MBRWT_HIP(hipSetDevice(c.device));
+    if (!ctx || (n_rows && !rows) || !read_offsets || !label_offsets) return invalid_argument();
+    return query(ctx, nullptr, "mbrwt_get_labels_batch", [&](Ctx &c, hipStream_t s) -> int {
         int rc;
-        // rows | read offsets | label offsets, one host-path workspace
-        if ((rc = ensure(c.ws_rows, (n_rows + 2 * (n_reads + 1)) * sizeof(uint64_t)))) return rc;
-        uint64_t *d_rows = reinterpret_cast<uint64_t *>(c.ws_rows.buf);
-        uint64_t *d_roff = d_rows + n_rows;
-        uint64_t *d_loff = d_roff + n_reads + 1;
-        if (n_rows) MBRWT_HIP(hipMemcpyAsync(d_rows, rows, n_rows * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
-        MBRWT_HIP(hipMemcpyAsync(d_roff, read_offsets, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice,
-                                 c.stream));
+        ClassifyStage d;
+        if ((rc = stage_classify(c, rows, n_rows, read_offsets, n_reads, d))) return rc;
         if ((rc = ensure(c.ws_out, std::max<uint64_t>(labels_cap, 1) * sizeof(uint32_t)))) return rc;
         uint64_t needed = 0;
-        rc = run_get_labels_batch(c, d_rows, n_rows, d_roff, n_reads, presence_ratio, d_loff,
-                                  reinterpret_cast<uint32_t *>(c.ws_out.buf), labels ? labels_cap : 0, &needed,
-                                  c.stream);
+        rc = run_get_labels_batch(c, d.rows, n_rows, d.read_offsets, n_reads, presence_ratio, d.label_offsets,
+                                  reinterpret_cast<uint32_t *>(c.ws_out.buf), labels ? labels_cap : 0, &needed, s);
         if (labels_needed) *labels_needed = needed;
         if (rc) return rc;
-        MBRWT_HIP(hipMemcpyAsync(label_offsets, d_loff, (n_reads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                                 c.stream));
+        MBRWT_HIP(hipMemcpyAsync(label_offsets, d.label_offsets, (n_reads + 1) * sizeof(uint64_t),
+                                 hipMemcpyDeviceToHost, s));
         if (needed)
-            MBRWT_HIP(hipMemcpyAsync(labels, c.ws_out.buf, needed * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
-        MBRWT_HIP(hipStreamSynchronize(c.stream));
+            MBRWT_HIP(hipMemcpyAsync(labels, c.ws_out.buf, needed * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        MBRWT_HIP(hipStreamSynchronize(s));
         return MBRWT_OK;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_get_labels_batch");
-        return MBRWT_ERR_INVALID;
-    }
+    });
 }
 
 int mbrwt_get_top_labels_batch_device(mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n_rows,
                                       const uint64_t *d_read_offsets, uint64_t n_reads, uint64_t num_top,
                                       uint64_t *d_label_offsets, uint32_t *d_labels, uint64_t *d_counts,
                                       uint64_t labels_cap, uint64_t *labels_needed, void *stream) {
-    if (!ctx || (n_rows && !d_rows) || !d_read_offsets || !d_label_offsets) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    std::lock_guard<std::mutex> lk(c.mu);
-    WsFence fence_(c.fence, reinterpret_cast<hipStream_t>(stream));
-    try {
-        MBRWT_HIP(hipSetDevice(c.device));
+    if (!ctx || (n_rows && !d_rows) || !d_read_offsets || !d_label_offsets) return invalid_argument();
+    return query(ctx, &stream, "mbrwt_get_top_labels_batch_device", [&](Ctx &c, hipStream_t s) {
         const bool out = d_labels && d_counts;
         return run_get_top_labels_batch(c, d_rows, n_rows, d_read_offsets, n_reads, num_top, d_label_offsets,
-                                        d_labels, d_counts, out ? labels_cap : 0, labels_needed,
-                                        reinterpret_cast<hipStream_t>(stream));
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_get_top_labels_batch_device");
-        return MBRWT_ERR_INVALID;
-    }
+                                        d_labels, d_counts, out ? labels_cap : 0, labels_needed, s);
+    });
 }
 
 int mbrwt_get_top_labels_batch(mbrwt_ctx *ctx, const uint64_t *rows, uint64_t n_rows, const uint64_t *read_offsets,
                                uint64_t n_reads, uint64_t num_top, uint64_t *label_offsets, uint32_t *labels,
                                uint64_t *counts, uint64_t labels_cap, uint64_t *labels_needed) {
-    if (!ctx || (n_rows && !rows) || !read_offsets || !label_offsets) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    std::lock_guard<std::mutex> lk(c.mu);
-    WsFence fence_(c.fence, c.stream);
-    try {
-        MBRWT_HIP(hipSetDevice(c.device));
+    if (!ctx || (n_rows && !rows) || !read_offsets || !label_offsets) return invalid_argument();
+    return query(ctx, nullptr, "mbrwt_get_top_labels_batch", [&](Ctx &c, hipStream_t s) -> int {
         int rc;
-        if ((rc = ensure(c.ws_rows, (n_rows + 2 * (n_reads + 1)) * sizeof(uint64_t)))) return rc;
-        uint64_t *d_rows = reinterpret_cast<uint64_t *>(c.ws_rows.buf);
-        uint64_t *d_roff = d_rows + n_rows;
-        uint64_t *d_loff = d_roff + n_reads + 1;
-        if (n_rows) MBRWT_HIP(hipMemcpyAsync(d_rows, rows, n_rows * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
-        MBRWT_HIP(hipMemcpyAsync(d_roff, read_offsets, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice,
-                                 c.stream));
+        ClassifyStage d;
+        if ((rc = stage_classify(c, rows, n_rows, read_offsets, n_reads, d))) return rc;
         // labels (u32) then counts (u64, 8-byte aligned) in the host-path output workspace
         const uint64_t lab_words = (std::max<uint64_t>(labels_cap, 1) + 1) & ~1ull;
         if ((rc = ensure(c.ws_out, lab_words * sizeof(uint32_t) + std::max<uint64_t>(labels_cap, 1) * 8))) return rc;
@@ -1570,35 +1330,26 @@ int mbrwt_get_top_labels_batch(mbrwt_ctx *ctx, const uint64_t *rows, uint64_t n_
         uint64_t *d_cnt = reinterpret_cast<uint64_t *>(d_lab + lab_words);
         uint64_t needed = 0;
         const bool out = labels && counts;
-        rc = run_get_top_labels_batch(c, d_rows, n_rows, d_roff, n_reads, num_top, d_loff, d_lab, d_cnt,
-                                      out ? labels_cap : 0, &needed, c.stream);
+        rc = run_get_top_labels_batch(c, d.rows, n_rows, d.read_offsets, n_reads, num_top, d.label_offsets, d_lab,
+                                      d_cnt, out ? labels_cap : 0, &needed, s);
         if (labels_needed) *labels_needed = needed;
         if (rc) return rc;
-        MBRWT_HIP(hipMemcpyAsync(label_offsets, d_loff, (n_reads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                                 c.stream));
+        MBRWT_HIP(hipMemcpyAsync(label_offsets, d.label_offsets, (n_reads + 1) * sizeof(uint64_t),
+                                 hipMemcpyDeviceToHost, s));
         if (needed) {
-            MBRWT_HIP(hipMemcpyAsync(labels, d_lab, needed * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
-            MBRWT_HIP(hipMemcpyAsync(counts, d_cnt, needed * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream));
+            MBRWT_HIP(hipMemcpyAsync(labels, d_lab, needed * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            MBRWT_HIP(hipMemcpyAsync(counts, d_cnt, needed * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         }
-        MBRWT_HIP(hipStreamSynchronize(c.stream));
+        MBRWT_HIP(hipStreamSynchronize(s));
         return MBRWT_OK;
-    } catch (...) {
-        set_error("unexpected exception in mbrwt_get_top_labels_batch");
-        return MBRWT_ERR_INVALID;
-    }
+    });
 }
 
 int mbrwt_count_work_device(mbrwt_ctx *ctx, const uint64_t *d_rows, uint64_t n, uint64_t *sum_visits,
                             uint64_t *sum_labels, void *stream) {
-    if (!ctx || (n && !d_rows)) {
-        set_error("invalid argument");
-        return MBRWT_ERR_INVALID;
-    }
-    Ctx &c = *C(ctx);
-    std::lock_guard<std::mutex> lk(c.mu);
-    WsFence fence_(c.fence, reinterpret_cast<hipStream_t>(stream));
-    MBRWT_HIP(hipSetDevice(c.device));
-    return run_count_work(c, d_rows, n, sum_visits, sum_labels, reinterpret_cast<hipStream_t>(stream));
+    if (!ctx || (n && !d_rows)) return invalid_argument();
+    return query(ctx, &stream, "mbrwt_count_work_device",
+                 [&](Ctx &c, hipStream_t s) { return run_count_work(c, d_rows, n, sum_visits, sum_labels, s); });
 }
 
 static int apply_option(Ctx &c, int option, int64_t value) {
@@ -1669,7 +1420,7 @@ int mbrwt_set_option(mbrwt_ctx *ctx, int option, int64_t value) {
     if (!ctx) return MBRWT_ERR_INVALID;
     Ctx &c = *C(ctx);
     std::lock_guard<std::mutex> lk(c.mu);
-    return apply_option(c, option, value);
+    return guarded("mbrwt_set_option", [&] { return apply_option(c, option, value); });
 }
 
 int mbrwt_take_timing(mbrwt_ctx *ctx, double *kernel_ms, uint64_t *launches) {

@@ -90,7 +90,7 @@ inline uint64_t cut_range_fit(uint64_t n, uint64_t a, uint64_t R, uint64_t align
     return std::min(n, a + lo * align);
 }
 
-// cut_rows_range for column-major data: labels(e) = the labels of the rows
+// RowsSource::cut (capi.cpp) for column-major data: labels(e) = the labels of the rows
 // [a, e), from the per-column cursors; `budget` = the device bytes a range
 // may take (capi.cpp: free less the reserve and the pending records, over
 // 1.2); a fixed range size (MBRWT_BUILD_ROWS_RANGE) is taken as it is
