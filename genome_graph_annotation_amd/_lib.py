@@ -27,6 +27,7 @@ MBRWT_OPT_KERNEL = 4
 MBRWT_OPT_ROWS_WALK = 8
 MBRWT_OPT_TEST_FAIL_CHUNK = 32  # test hook (host-buffer path)
 MBRWT_OPT_COMPACT_CUS = 64  # row records: compaction on a CU-masked stream (measurement)
+MBRWT_OPT_COLUMNS_CHUNK = 128  # test hook: rows per internal chunk of get_columns (0 = auto)
 
 MBRWT_BUILD_LAYOUT = 1
 MBRWT_BUILD_PARTITIONER = 2
@@ -236,6 +237,10 @@ SIGNATURES = {
                                                 C.c_uint64, C.c_void_p, C.c_void_p]),
     "mbrwt_get_column": (C.c_int, [C.c_void_p, C.c_uint64, u64p, C.c_uint64, u64p]),
     "mbrwt_get_column_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_void_p]),
+    "mbrwt_get_columns": (C.c_int, [C.c_void_p, u64p, C.c_uint64, C.c_uint64, C.c_uint64, u64p, u64p, C.c_uint64,
+                                    u64p]),
+    "mbrwt_get_columns_device": (C.c_int, [C.c_void_p, u64p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                           C.c_void_p, C.c_uint64, u64p, C.c_void_p]),
     "mbrwt_get_batch": (C.c_int, [C.c_void_p, u64p, u64p, C.c_uint64, u8p]),
     "mbrwt_get_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "mbrwt_count_labels_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),

@@ -606,6 +606,57 @@ class BRWTDevice:
         L.check(st, "mbrwt_get_column_device")
         return int(need.value)
 
+    def _columns_arg(self, columns):
+        # (columns array or None, its ctypes pointer or None, n_columns)
+        if columns is None:
+            return None, None, self.num_columns()
+        columns = np.ascontiguousarray(columns, dtype=np.uint64)
+        return columns, _p(columns, C.c_uint64), len(columns)
+
+    def get_columns(self, columns=None, row_begin=0, row_end=None):
+        """mbrwt_get_columns: the sparse columns of the rows [row_begin,
+        row_end) as (offsets u64 [n_columns + 1], rows u64) -- slot j's
+        ascending absolute row ids are rows[offsets[j]:offsets[j + 1]], in the
+        caller's order of `columns` (None: every column in order).  The sizing
+        call, then the filling call."""
+        columns, cp, k = self._columns_arg(columns)
+        row_end = self.num_rows() if row_end is None else int(row_end)
+        offsets = np.zeros(k + 1, dtype=np.uint64)
+        need = C.c_uint64(0)
+        st = L.lib().mbrwt_get_columns(self._h, cp, k, int(row_begin), row_end, _p(offsets, C.c_uint64), None, 0,
+                                       C.byref(need))
+        if st != L.MBRWT_ERR_CAPACITY:
+            L.check(st, "mbrwt_get_columns")
+            return offsets, np.zeros(0, dtype=np.uint64)
+        out = np.zeros(max(1, need.value), dtype=np.uint64)
+        L.check(L.lib().mbrwt_get_columns(self._h, cp, k, int(row_begin), row_end, _p(offsets, C.c_uint64),
+                                          _p(out, C.c_uint64), len(out), C.byref(need)), "mbrwt_get_columns")
+        return offsets, out[: need.value]
+
+    def get_columns_device(self, columns, row_begin, row_end, offsets_t, rows_t, stream=None):
+        """Device variant: `columns` stays a host array (or None); offsets_t =
+        64-bit cuda tensor [n_columns + 1], rows_t = 64-bit cuda tensor of
+        capacity >= the total (None: size only).  Returns the total; raises on
+        capacity with .needed set (offsets_t is complete then)."""
+        columns, cp, k = self._columns_arg(columns)
+        row_end = self.num_rows() if row_end is None else int(row_end)
+        need = C.c_uint64(0)
+        st = L.lib().mbrwt_get_columns_device(self._h, cp, k, int(row_begin), row_end, offsets_t.data_ptr(),
+                                              rows_t.data_ptr() if rows_t is not None else None,
+                                              rows_t.numel() if rows_t is not None else 0, C.byref(need),
+                                              stream if stream is not None else None)
+        if st == L.MBRWT_ERR_CAPACITY:
+            e = L.MBRWTError(st, "mbrwt_get_columns_device")
+            e.needed = int(need.value)
+            raise e
+        L.check(st, "mbrwt_get_columns_device")
+        return int(need.value)
+
+    def to_sparse_columns(self):
+        """The whole matrix as (col_offsets, col_rows): what from_sparse_columns
+        and shape_from_sparse_columns take."""
+        return self.get_columns()
+
     # -- device-buffer queries (torch tensors as plumbing) ---------------------
     def get_rows_device(self, rows_t, offsets_t, cols_t, stream=None):
         """rows_t: uint64/int64 cuda tensor [n]; offsets_t: [n+1] 64-bit; cols_t:

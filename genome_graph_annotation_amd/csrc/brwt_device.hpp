@@ -125,6 +125,25 @@ inline void check_status(int status, const char *where) {
     throw MBRWTException(status, where);
 }
 
+// mbrwt_get_columns as vectors: slot j = the ascending rows of [begin, end)
+// that carry columns[j] (the sizing call, then the filling call)
+inline std::vector<std::vector<uint64_t>> columns_of(mbrwt_ctx *ctx, const std::vector<uint64_t> &columns,
+                                                     uint64_t begin, uint64_t end, const char *where) {
+    std::vector<uint64_t> offsets(columns.size() + 1, 0), rows;
+    uint64_t need = 0;
+    int st = mbrwt_get_columns(ctx, columns.data(), columns.size(), begin, end, offsets.data(), nullptr, 0, &need);
+    if (st == MBRWT_ERR_CAPACITY) {
+        rows.resize(need);
+        st = mbrwt_get_columns(ctx, columns.data(), columns.size(), begin, end, offsets.data(), rows.data(),
+                               rows.size(), &need);
+    }
+    check_status(st, where);
+    std::vector<std::vector<uint64_t>> out(columns.size());
+    for (size_t j = 0; j < columns.size(); ++j)
+        out[j].assign(rows.begin() + offsets[j], rows.begin() + offsets[j + 1]);
+    return out;
+}
+
 // A BRWT whose queries run on an MI355X (the reference's BRWT::get_row /
 // BRWT::get, BRWT.cpp:9-53).
 class BRWTDevice : public BinaryMatrix {
@@ -290,6 +309,13 @@ class BRWTDevice : public BinaryMatrix {
         check_status(mbrwt_get_column(ctx_.get(), column, rows.data(), rows.size(), &need), "BRWTDevice::get_column");
         rows.resize(need);
         return rows;
+    }
+
+    // the sparse columns of the rows [begin, end), in the order of `columns`
+    // (mbrwt_get_columns: one pass over the row records for all of them)
+    std::vector<std::vector<Row>> get_columns(const std::vector<Column> &columns, Row begin, Row end) const {
+        if (!ctx_) throw std::out_of_range("get_columns on an empty BRWT");
+        return columns_of(ctx_.get(), columns, begin, end, "BRWTDevice::get_columns");
     }
 
     std::vector<std::vector<Column>> get_rows(const std::vector<Row> &rows) const override {
@@ -558,6 +584,10 @@ class BRWTMultiDevice : public BinaryMatrix {
         check_status(mbrwt_get_column(r0(), column, rows.data(), rows.size(), &need), "BRWTMultiDevice::get_column");
         rows.resize(need);
         return rows;
+    }
+    std::vector<std::vector<Row>> get_columns(const std::vector<Column> &columns, Row begin, Row end) const {
+        if (!m_) throw std::out_of_range("get_columns on an empty BRWT");
+        return columns_of(r0(), columns, begin, end, "BRWTMultiDevice::get_columns");
     }
     std::vector<std::vector<Column>> get_rows(const std::vector<Row> &rows) const override {
         std::vector<uint64_t> offsets;

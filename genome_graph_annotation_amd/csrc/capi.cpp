@@ -113,7 +113,8 @@ static void release(Ctx *c) {
     }
     for (Workspace *w : {&c->ws_temp, &c->ws_counts, &c->ws_ovf, &c->ws_scan, &c->ws_rows, &c->ws_out, &c->ws_sort,
                          &c->ws_cls_off, &c->ws_cls_cols, &c->ws_class, &c->ws_sh_keys, &c->ws_sh_local, &c->ws_sh_cnt,
-                         &c->ws_sh_sort, &c->ws_sh_tmp, &c->ws_cols16})
+                         &c->ws_sh_sort, &c->ws_sh_tmp, &c->ws_cols16, &c->ws_gc_slots, &c->ws_gc_rows,
+                         &c->ws_gc_pairs, &c->ws_gc_tmp, &c->ws_gc_off})
         if (w->buf) (void)hipFree(w->buf);
     free_host_pipe(c->pipe);
     if (c->d_scalars) (void)hipFree(c->d_scalars);
@@ -1236,6 +1237,69 @@ int mbrwt_get_column(mbrwt_ctx *ctx, uint64_t column, uint64_t *rows, uint64_t r
     });
 }
 
+// mbrwt_get_columns[_device]: the host checks, before any launch
+static int check_columns_call(const Ctx &c, const uint64_t *columns, uint64_t n_columns, uint64_t row_begin,
+                              uint64_t row_end) {
+    const uint64_t m = c.tree.num_columns;
+    if (!columns && n_columns && n_columns != m) {
+        set_error("get_columns: columns == NULL asks for every column, n_columns must be num_columns");
+        return MBRWT_ERR_INVALID;
+    }
+    if (row_begin > row_end || row_end > c.tree.num_rows) {
+        set_error("row window out of range");
+        return MBRWT_ERR_RANGE;
+    }
+    if (!columns) return MBRWT_OK;
+    for (uint64_t j = 0; j < n_columns; ++j)
+        if (columns[j] >= m) {
+            set_error("column out of range");
+            return MBRWT_ERR_RANGE;
+        }
+    std::vector<bool> seen(m, false);
+    for (uint64_t j = 0; j < n_columns; ++j) {
+        if (seen[columns[j]]) {
+            set_error("get_columns: column " + std::to_string(columns[j]) + " listed twice");
+            return MBRWT_ERR_INVALID;
+        }
+        seen[columns[j]] = true;
+    }
+    return MBRWT_OK;
+}
+
+int mbrwt_get_columns_device(mbrwt_ctx *ctx, const uint64_t *columns, uint64_t n_columns, uint64_t row_begin,
+                             uint64_t row_end, uint64_t *d_offsets, uint64_t *d_rows, uint64_t rows_cap,
+                             uint64_t *rows_needed, void *stream) {
+    if (!ctx || !d_offsets) return invalid_argument();
+    return query(ctx, &stream, "mbrwt_get_columns_device", [&](Ctx &c, hipStream_t s) -> int {
+        if (const int rc = check_columns_call(c, columns, n_columns, row_begin, row_end)) return rc;
+        return run_get_columns(c, columns, n_columns, row_begin, row_end, d_offsets, d_rows, rows_cap, rows_needed,
+                               nullptr, s);
+    });
+}
+
+int mbrwt_get_columns(mbrwt_ctx *ctx, const uint64_t *columns, uint64_t n_columns, uint64_t row_begin,
+                      uint64_t row_end, uint64_t *offsets, uint64_t *rows, uint64_t rows_cap, uint64_t *rows_needed) {
+    if (!ctx || !offsets) return invalid_argument();
+    return query(ctx, nullptr, "mbrwt_get_columns", [&](Ctx &c, hipStream_t s) -> int {
+        int rc;
+        if ((rc = check_columns_call(c, columns, n_columns, row_begin, row_end))) return rc;
+        if ((rc = ensure(c.ws_gc_off, (n_columns + 1) * sizeof(uint64_t)))) return rc;
+        uint64_t *d_off = reinterpret_cast<uint64_t *>(c.ws_gc_off.buf);
+        uint64_t needed = 0;
+        // (the staging buffer is sized by the result, not by rows_cap)
+        rc = run_get_columns(c, columns, n_columns, row_begin, row_end, d_off, nullptr, rows ? rows_cap : 0, &needed,
+                             rows ? &c.ws_out : nullptr, s);
+        if (rows_needed) *rows_needed = needed;
+        if (rc && rc != MBRWT_ERR_CAPACITY) return rc;
+        // the offsets are complete on a capacity refusal too (the sizing call)
+        MBRWT_HIP(hipMemcpyAsync(offsets, d_off, (n_columns + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        if (!rc && needed)
+            MBRWT_HIP(hipMemcpyAsync(rows, c.ws_out.buf, needed * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        MBRWT_HIP(hipStreamSynchronize(s));
+        return rc;
+    });
+}
+
 int mbrwt_get_batch_device(mbrwt_ctx *ctx, const uint64_t *d_rows, const uint64_t *d_cols, uint64_t n,
                            uint8_t *d_out, void *stream) {
     if (!ctx || (n && (!d_rows || !d_cols || !d_out))) return invalid_argument();
@@ -1369,6 +1433,10 @@ static int apply_option(Ctx &c, int option, int64_t value) {
         return MBRWT_OK;
     case MBRWT_OPT_TEST_FAIL_CHUNK:
         c.test_fail_chunk = value < 0 ? -1 : value;
+        return MBRWT_OK;
+    case MBRWT_OPT_COLUMNS_CHUNK:
+        if (value < 0) return MBRWT_ERR_INVALID;
+        c.columns_chunk = (uint64_t)value;
         return MBRWT_OK;
     case MBRWT_OPT_COMPACT_CUS: {
         if (value < 0 || value > 31) return MBRWT_ERR_INVALID;

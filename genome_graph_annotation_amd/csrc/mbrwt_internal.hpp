@@ -406,6 +406,10 @@ struct Ctx {
     Workspace ws_cls_off, ws_cls_cols;  // get_labels batch: the rows' CSR
     Workspace ws_class;                 // record classes: the batch's classes (rows_class.hip)
     Workspace ws_cols16;                // mbrwt_get_rows16* without row records: the u32 labels before narrowing
+    // mbrwt_get_columns (rows_columns.hip): slot map / totals / cursors, the chunk's
+    // per-row counts, its pairs (or, without row records, one staged column),
+    // scan and sort scratch, the host form's offsets
+    Workspace ws_gc_slots, ws_gc_rows, ws_gc_pairs, ws_gc_tmp, ws_gc_off;
     uint64_t *h_scalars = nullptr;      // pinned: [0] total, [1] overflow count, [2] error
     uint64_t *d_scalars = nullptr;      // device twin
     HostPipe *pipe = nullptr;           // streams, slots and staging of mbrwt_get_rows (lazily created)
@@ -416,6 +420,7 @@ struct Ctx {
     int kernel_variant = 0;             // MBRWT_OPT_KERNEL: 0 the default families, 1 the lane-per-row node kernel
     int rows_walk = 0;                  // MBRWT_OPT_ROWS_WALK (6: the non-odometer walk on uniform trees)
     int64_t test_fail_chunk = -1;       // MBRWT_OPT_TEST_FAIL_CHUNK (test hook: host_get_rows fails at that chunk)
+    uint64_t columns_chunk = 0;         // MBRWT_OPT_COLUMNS_CHUNK (test hook: rows per chunk of get_columns; 0 = auto)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // MBRWT_OPT_COMPACT_CUS (r06, VERDICT r05 #1a): k_compact_tiles on a
     // stream masked to compact_cus of every 32 CUs, ordered after the
@@ -716,6 +721,15 @@ inline bool packt_enabled() { return pack_enabled() && (build_tuning().node_kind
 // column query (column.hip): ascending rows of `column` into d_rows (u64)
 int run_get_column(Ctx &c, uint64_t column, uint64_t *d_rows, uint64_t rows_cap, uint64_t *rows_needed,
                    hipStream_t s);
+// batched column query (rows_columns.hip): the ascending rows
+// of [row_begin, row_end) per requested slot as a CSR, d_offsets (n_columns +
+// 1) complete also on MBRWT_ERR_CAPACITY.  `columns`: host, checked by the
+// caller (in range, no duplicate), null = every column in order.  stage !=
+// null: the rows go to stage->buf, grown to the total once it is known and
+// within rows_cap (the host form), instead of d_rows.
+int run_get_columns(Ctx &c, const uint64_t *columns, uint64_t n_columns, uint64_t row_begin, uint64_t row_end,
+                    uint64_t *d_offsets, uint64_t *d_rows, uint64_t rows_cap, uint64_t *rows_needed, Workspace *stage,
+                    hipStream_t s);
 const char *traverse_kernel_name(const Ctx &c);  // the kernel mbrwt_get_rows* launches
 // mbrwt_get_rows: host row ids -> host CSR, chunked and pipelined (hostpipe.cpp)
 // (width: bytes per label of cols, 4 or 2)

@@ -43,6 +43,7 @@
 
 #include "device_access.hpp"
 #include "mbrwt_internal.hpp"
+#include "rows_columns.hpp"
 #include "rows_emit.hpp"
 #include "rows_select.hpp"
 #include "wave_scan.hpp"
@@ -723,6 +724,17 @@ struct VarHasColumn {
     }
 };
 
+// mbrwt_get_columns (rows_columns.hip): a row's labels as a RowLabels
+struct VarRowLabels {
+    VarView v;
+    const uint32_t *units;
+    template <class Leaf>
+    __device__ bool operator()(uint64_t row, Leaf leaf) const {
+        var_row(v, units, row, leaf);
+        return true;
+    }
+};
+
 VarView var_view(const Ctx &c) {
     VarView v;
     v.lines = (uint64_t)(uintptr_t)c.rows.var_lines;
@@ -891,6 +903,8 @@ int var_count(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_counts, ui
     }
     return finish_record_call(c, s, visits, labels);
 }
+
+GcSweeps var_gc_sweeps(const Ctx &c) { return gc_sweeps(VarRowLabels{var_view(c), c.rows.d_var_units}); }
 
 int var_get_column(Ctx &c, uint64_t column, uint64_t *d_rows, uint64_t rows_cap, uint64_t *rows_needed,
                    hipStream_t s) {

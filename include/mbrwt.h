@@ -627,6 +627,50 @@ int mbrwt_get_column_device(mbrwt_ctx *ctx, uint64_t column, uint64_t *d_rows, u
                             uint64_t *rows_needed, void *stream);
 
 /*
+ * Batched column extraction: the sparse columns of the row window [row_begin,
+ * row_end) for many columns at once -- the inverse of
+ * mbrwt_create_from_sparse_columns (the reference's ColumnCompressed form,
+ * ascending row ids per column).  The result is a CSR by REQUESTED SLOT:
+ * rows[offsets[j] .. offsets[j + 1]) = the ascending absolute row ids r,
+ * row_begin <= r < row_end, that carry columns[j], i.e.
+ * mbrwt_get_column(columns[j]) clipped to the window; offsets[0] = 0, n_columns
+ * + 1 offsets.  Slots come in the caller's order, which need not ascend.
+ *   columns     a HOST array (in both forms, like `counts` of
+ *               mbrwt_unpack_segments_device).  NULL = every column 0 ..
+ *               num_columns - 1 in order; n_columns must then equal
+ *               num_columns.  n_columns == 0 is legal: offsets[0] = 0,
+ *               *rows_needed = 0, MBRWT_OK.
+ *   capacity    a total above rows_cap, or rows == NULL with a non-zero total,
+ *               returns MBRWT_ERR_CAPACITY: *rows_needed (may be NULL) holds
+ *               the total, offsets is COMPLETE (the sizing call yields every
+ *               column's size) and rows is untouched.
+ *   errors      a column >= num_columns, row_begin > row_end or row_end >
+ *               num_rows -> MBRWT_ERR_RANGE; a column listed twice ->
+ *               MBRWT_ERR_INVALID (the message names it); NULL ctx or offsets
+ *               -> MBRWT_ERR_INVALID, with or without a GPU; columns == NULL
+ *               with n_columns neither 0 nor num_columns -> MBRWT_ERR_INVALID.
+ *               All checked on the host before any launch.
+ * On row records (layout ROWS, and BOTH through its records) the records are
+ * swept twice whatever n_columns is -- a count sweep (it alone answers the
+ * sizing call) and an emit sweep -- or three times when the window takes more
+ * than one internal chunk (a chunk: at most 2^32 rows and 2^31 - 1 result
+ * rows, sized from the free device memory: 16 bytes per result row of the
+ * chunk -- 8 for a single column -- plus the sort's histograms, and 4 per row
+ * of it).  Contexts without row records (layout NODES, row
+ * shards) answer with mbrwt_get_column's work per column, twice.
+ * Device form: the conventions of mbrwt_get_column_device (the context's
+ * workspace fence; the results are complete on return); it synchronises
+ * `stream` a bounded number of times per chunk, never per column, on row
+ * records.  Host form: the result is staged in a context workspace (8 bytes
+ * per returned row) and downloaded -- the window is how a caller bounds that.
+ */
+int mbrwt_get_columns(mbrwt_ctx *ctx, const uint64_t *columns, uint64_t n_columns, uint64_t row_begin,
+                      uint64_t row_end, uint64_t *offsets, uint64_t *rows, uint64_t rows_cap, uint64_t *rows_needed);
+int mbrwt_get_columns_device(mbrwt_ctx *ctx, const uint64_t *columns /* HOST, or NULL */, uint64_t n_columns,
+                             uint64_t row_begin, uint64_t row_end, uint64_t *d_offsets /* n_columns + 1 */,
+                             uint64_t *d_rows, uint64_t rows_cap, uint64_t *rows_needed, void *stream);
+
+/*
  * StaticBinRelAnnotator::count_labels (annotate_static.cpp:149-162) fused on
  * the device: counts[c] (num_columns uint64, zeroed by the call) = number of
  * rows among d_rows[0..n) that carry column c.  Device buffers.
@@ -769,6 +813,9 @@ int mbrwt_unpack_offsets_device(const void *d_base, uint32_t nseg, uint64_t seg_
 #define MBRWT_OPT_TEST_FAIL_CHUNK 32 /* test hook: mbrwt_get_rows (host buffers) fails with MBRWT_ERR_NOMEM
                                         when it reaches chunk `value` of the batch (-1: never) -- the error
                                         path's drain of the chunks already in flight is tested with it */
+#define MBRWT_OPT_COLUMNS_CHUNK 128 /* test hook: rows per internal chunk of mbrwt_get_columns* on row records
+                                       (0 = auto, from the free device memory) -- the chunk cursors are tested
+                                       with it at small shapes */
 int mbrwt_set_option(mbrwt_ctx *ctx, int option, int64_t value);
 
 /* Traversal-kernel time accumulated while MBRWT_OPT_TIMING is on (ms, launches); resets the sums. */
