@@ -46,6 +46,19 @@ MBRWT_KIND_PACK = 2
 MBRWT_KIND_PACK2 = 4
 MBRWT_KIND_PACKT = 8
 MBRWT_KIND_ALL = 15
+MBRWT_NODE_LEAF = 0
+MBRWT_NODE_PLANE = 1
+MBRWT_NODE_MASK8 = 2
+MBRWT_NODE_MASK16 = 3
+MBRWT_NODE_MASK32 = 4
+MBRWT_NODE_MASK64 = 5
+MBRWT_NODE_FOLDED = 6
+MBRWT_NODE_PACK = 7
+MBRWT_NODE_PACK2 = 8
+MBRWT_NODE_PACKT = 9
+MBRWT_NODE_PACKT_IN = 10
+NODE_KIND_NAMES = {0: "LEAF", 1: "PLANE", 2: "MASK8", 3: "MASK16", 4: "MASK32", 5: "MASK64", 6: "FOLDED", 7: "PACK",
+                   8: "PACK2", 9: "PACKT", 10: "PACKT_IN"}
 MBRWT_ROWS_FAST = 0
 MBRWT_ROWS_COMPACT = 1
 MBRWT_PARTITIONER_BASIC = 0
@@ -211,6 +224,7 @@ SIGNATURES = {
                                                           C.c_void_p, C.c_uint64, u64p, C.c_void_p]),
     "mbrwt_layout": (C.c_int, [C.c_void_p]),
     "mbrwt_rows_stats": (C.c_int, [C.c_void_p, u64p]),
+    "mbrwt_node_info": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, u64p]),
     "mbrwt_rows_classes": (C.c_int, [C.c_void_p, u64p]),
     "mbrwt_tree_parse": (C.c_int, [u8p, C.c_uint64, u64p, C.POINTER(C.c_void_p)]),
     "mbrwt_tree_serialize": (C.c_int, [C.POINTER(TreeDesc), u8p, C.c_uint64, u64p]),

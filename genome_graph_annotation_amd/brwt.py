@@ -527,6 +527,17 @@ class BRWTDevice:
             d["classes"], d["class_bits"], d["class_index_bytes"], d["class_sample_distinct"] = (int(v) for v in cl)
         return d
 
+    def node_info(self, dnode, shard=0):
+        """What was built for device node `dnode` of the per-node images
+        (mbrwt_node_info; diagnostics, launches nothing): a dict of kind (a
+        name of _lib.NODE_KIND_NAMES), arity, stride and length.  dnode 0 is
+        the super-root, dnode u + 1 is node u of the tree description; `shard`
+        picks the row shard of a sharded context."""
+        out = (C.c_uint64 * 4)()
+        L.check(L.lib().mbrwt_node_info(self._h, int(shard), int(dnode), out), "mbrwt_node_info")
+        return {"kind": L.NODE_KIND_NAMES.get(int(out[0]), "?"), "arity": int(out[1]), "stride": int(out[2]),
+                "length": int(out[3])}
+
     # -- host-buffer queries --------------------------------------------------
     def get_rows(self, rows):
         """Batched BRWT::get_row (BRWT.cpp:26-53) -> (offsets[n+1], cols)."""

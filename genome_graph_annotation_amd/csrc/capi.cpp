@@ -1177,6 +1177,34 @@ int mbrwt_rows_classes(const mbrwt_ctx *ctx, uint64_t out[4]) {
     out[3] = r.class_sample_distinct;
     return MBRWT_OK;
 }
+static_assert(KIND_LEAF == MBRWT_NODE_LEAF && KIND_PLANE == MBRWT_NODE_PLANE && KIND_MASK8 == MBRWT_NODE_MASK8 &&
+                  KIND_MASK64 == MBRWT_NODE_MASK64 && KIND_FOLDED == MBRWT_NODE_FOLDED &&
+                  KIND_PACK == MBRWT_NODE_PACK && KIND_PACK2 == MBRWT_NODE_PACK2 && KIND_PACKT == MBRWT_NODE_PACKT &&
+                  KIND_PACKT_IN == MBRWT_NODE_PACKT_IN,
+              "the MBRWT_NODE_* values of include/mbrwt.h are the image kinds");
+int mbrwt_node_info(const mbrwt_ctx *ctx, uint64_t shard, uint32_t dnode, uint64_t out[4]) {
+    if (!ctx || !out) return MBRWT_ERR_INVALID;
+    const Ctx *c = C(ctx);
+    if (shard >= std::max<uint64_t>(1, c->shards.size())) {
+        set_error("shard out of range");
+        return MBRWT_ERR_RANGE;
+    }
+    if (!c->shards.empty()) c = c->shards[shard];
+    if (c->nodes_freed) {
+        set_error("context has no node images");
+        return MBRWT_ERR_UNSUPPORTED;
+    }
+    if (dnode >= c->tree.nodes.size()) {
+        set_error("dnode out of range");
+        return MBRWT_ERR_RANGE;
+    }
+    const DevNode &d = c->tree.nodes[dnode];
+    out[0] = d.kind;
+    out[1] = d.arity;
+    out[2] = d.stride;
+    out[3] = d.length;
+    return MBRWT_OK;
+}
 int mbrwt_device(const mbrwt_ctx *ctx) { return ctx ? C(ctx)->device : -1; }
 uint64_t mbrwt_num_shards(const mbrwt_ctx *ctx) { return ctx ? std::max<uint64_t>(1, C(ctx)->shards.size()) : 0; }
 

@@ -245,7 +245,7 @@ int run_get_column(Ctx &c, uint64_t column, uint64_t *d_rows, uint64_t rows_cap,
     const uint64_t total = c.h_scalars[0] + c.h_scalars[1];
     if (rows_needed) *rows_needed = total;
     if (total > rows_cap || (total && !d_rows)) {
-        set_error("row buffer too small (see rows_needed)");
+        set_error("rows_cap too small");
         return MBRWT_ERR_CAPACITY;
     }
     if (!total) return MBRWT_OK;

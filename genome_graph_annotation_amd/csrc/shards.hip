@@ -386,27 +386,37 @@ int sharded_get_column(Ctx &c, uint64_t column, uint64_t *d_rows, uint64_t rows_
         set_error("column out of range");
         return MBRWT_ERR_RANGE;
     }
+    // Size first: a refused call leaves the caller's rows untouched
+    // (include/mbrwt.h), so no shard may write before the total is known to
+    // fit.  The sizing call of a shard is the counting half of its query; the
+    // writing call below counts again: a call that succeeds takes about half
+    // as long again (4 shards of 10^6 rows, a column of 800,502 rows, one
+    // MI355X: 1.04 ms against the 0.70 ms of writing as it went).
+    const uint32_t K = (uint32_t)c.shards.size();
+    std::vector<uint64_t> need(K, 0);
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < K; ++k) {
+        const int rc = run_get_column(*c.shards[k], column, nullptr, 0, &need[k], s);
+        if (rc && rc != MBRWT_ERR_CAPACITY) return rc;
+        total += need[k];
+    }
+    if (rows_needed) *rows_needed = total;
+    if (total > rows_cap || (total && !d_rows)) {
+        set_error("rows_cap too small");
+        return MBRWT_ERR_CAPACITY;
+    }
     uint64_t at = 0;
-    bool short_cap = false;
-    for (uint32_t k = 0; k < c.shards.size(); ++k) {
-        uint64_t need = 0;
-        const uint64_t room = (!short_cap && d_rows && rows_cap > at) ? rows_cap - at : 0;
-        int rc = run_get_column(*c.shards[k], column, room ? d_rows + at : nullptr, room, &need, s);
-        if (rc == MBRWT_ERR_CAPACITY) {
-            short_cap = true;
-        } else if (rc) {
-            return rc;
-        } else if (need && k) {
-            hipLaunchKernelGGL(k_add_u64, dim3(grid_for(need)), dim3(256), 0, s, d_rows + at, nullptr, need,
+    for (uint32_t k = 0; k < K; ++k) {
+        if (!need[k]) continue;
+        uint64_t got = 0;
+        const int rc = run_get_column(*c.shards[k], column, d_rows + at, need[k], &got, s);
+        if (rc) return rc;
+        if (k) {
+            hipLaunchKernelGGL(k_add_u64, dim3(grid_for(got)), dim3(256), 0, s, d_rows + at, nullptr, got,
                                (unsigned long long)k * c.shard_rows);
             MBRWT_HIP(hipGetLastError());
         }
-        at += need;
-    }
-    if (rows_needed) *rows_needed = at;
-    if (short_cap) {
-        set_error("rows_cap too small");
-        return MBRWT_ERR_CAPACITY;
+        at += got;
     }
     return MBRWT_OK;
 }

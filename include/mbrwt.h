@@ -378,6 +378,33 @@ int mbrwt_rows_stats(const mbrwt_ctx *ctx, uint64_t out[8]);
    sampled).  With classes, mbrwt_rows_stats describes the dictionary (one
    record per class, S = 1).  MBRWT_ERR_UNSUPPORTED without row records. */
 int mbrwt_rows_classes(const mbrwt_ctx *ctx, uint64_t out[4]);
+/* Diagnostics: what was built for one node of the per-node images (read-only;
+   launches nothing).  dnode 0 is the super-root, dnode u + 1 is node u of the
+   tree description (BFS numbering); `shard` picks the row shard of a sharded
+   context (0 .. mbrwt_num_shards - 1) and must be 0 otherwise.  out[0] kind
+   (MBRWT_NODE_*), [1] arity, [2] stride -- bytes per 32-position block of a
+   PLANE node, 64 for a PACK node, positions per 64-byte block (1..8) for a
+   PACK2 / PACKT node, 0 otherwise --, [3] length: the positions of the node's
+   image, i.e. the rows that reach the node (0 for a leaf and for a folded
+   root).  MASK8..MASK64: every child is a leaf, one mask of 1 / 2 / 4 / 8
+   bytes per position.  FOLDED: the root whose children the super-root holds
+   over the row positions.  A node that is MBRWT_NODE_PACKT_IN, or a
+   PACK / MASK8 node below a PACK2 or PACK node, has a record but no image of
+   its own.  MBRWT_ERR_RANGE for a dnode or shard that does not exist,
+   MBRWT_ERR_UNSUPPORTED on a context that dropped its node images
+   (MBRWT_LAYOUT_ROWS). */
+#define MBRWT_NODE_LEAF 0
+#define MBRWT_NODE_PLANE 1
+#define MBRWT_NODE_MASK8 2
+#define MBRWT_NODE_MASK16 3
+#define MBRWT_NODE_MASK32 4
+#define MBRWT_NODE_MASK64 5
+#define MBRWT_NODE_FOLDED 6
+#define MBRWT_NODE_PACK 7
+#define MBRWT_NODE_PACK2 8
+#define MBRWT_NODE_PACKT 9
+#define MBRWT_NODE_PACKT_IN 10
+int mbrwt_node_info(const mbrwt_ctx *ctx, uint64_t shard, uint32_t dnode, uint64_t out[4]);
 
 /* ---- multi-device (one process, N GPUs) --------------------------------
  * A replica of the tree on every device of `devices` (n entries; a device

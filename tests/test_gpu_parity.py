@@ -268,7 +268,10 @@ def test_get_column_reference_grids(oracle_mod, kind, build):
     (2000, 70, 0.3, "basic", 33),      # MASK64 leaf parents
     (2000, 200, 0.02, "basic", 16),    # MASK16
     (4000, 9, 0.5, "basic", 8),        # leaves directly under a PLANE node (8 + 1 columns)
-    (70_000, 5, 0.9, "basic", 2),      # long dense columns, several lift levels
+    # long dense columns; under the default node kinds the folded root and its PACKT children cut the
+    # path to one lift (through the super-root): the lifts through several levels, and every image
+    # kind at its kernel edges, are tests/test_gpu_column_edges.py's
+    (70_000, 5, 0.9, "basic", 2),
 ])
 def test_get_column_random(oracle_mod, n, m, dens, part, arity):
     O = oracle_mod
