@@ -206,7 +206,7 @@ struct Tree {
     uint32_t push_frames = 0;               // max stack frames of the fast kernels (non-TERM PLANE nodes on a path)
     uint32_t lds_records = 0;               // last non-leaf dnode id + 1 (node records worth staging in LDS)
     // k_traverse_p2w (the super-root's children all KIND_PACK2): the compact
-    // table it stages in LDS (layout: query.hip "P2W table"), empty otherwise
+    // table it stages in LDS (layout: "P2W table" above), empty otherwise
     std::vector<uint32_t> p2w_table;
     bool has_packt = false;                 // some node is KIND_PACKT (general kernels: lane kernel only)
     std::vector<uint32_t> ptw_table;        // k_traverse_ptw's table (layout above), empty otherwise
@@ -620,8 +620,10 @@ int hip_fail(hipError_t e, const char *what);
         if (_e != hipSuccess) return ::mbrwt::hip_fail(_e, #call); \
     } while (0)
 
+// call plumbing (calls.cpp): shared by the drivers of query.hip,
+// nodes_rowblock.hip, rows.hip, rows_var.hip, rows_columns.hip, shards.hip,
+// classify.hip and hostpipe.cpp
 int ensure(Workspace &w, size_t bytes);
-// plumbing of the get_rows drivers (query.hip, rows.hip, rows_var.hip; defined in query.hip)
 // *blocks = the workgroups of `fn` (`threads` threads, `lds` bytes of dynamic
 // LDS) resident on the device, at most occ_cap per CU (0 = no cap); owns Ctx::rb_*
 int resident_workgroups(Ctx &c, const void *fn, uint32_t threads, size_t lds, int occ_cap, uint64_t *blocks);
@@ -632,11 +634,15 @@ int timing_events(Ctx &c, bool async, hipEvent_t *e0, hipEvent_t *e1);
 // the kernel time (ev0..ev1) taken, the status mapped to a return code + message
 //   row-record block {total, status}; `fallback`: the message of any other status
 int finish_rows_call(Ctx &c, uint64_t *needed, const char *fallback, hipStream_t s);
-//   a record point query's counters (get_batch, count_labels, the work count):
-//   [2] bit 0 -> MBRWT_ERR_RANGE, else [3] visits and [4] labels where asked
-int finish_record_call(Ctx &c, hipStream_t s, uint64_t *visits = nullptr, uint64_t *labels = nullptr);
 //   node-image block {total, overflow rows, error bits}
 int finish_nodes_call(Ctx &c, uint64_t cap, uint64_t *needed, uint64_t *overflow, hipStream_t s);
+// end of a point query (get_batch, count_labels, the work count): the launch
+// check, the counters to the host, the stream synchronised (no timing), [2]
+// mapped to a return code, else [3] visits and [4] labels where asked
+//   record protocol: bit 0 -> MBRWT_ERR_RANGE
+int finish_record_call(Ctx &c, hipStream_t s, uint64_t *visits = nullptr, uint64_t *labels = nullptr);
+//   node protocol: node_error_code
+int finish_node_point_call(Ctx &c, hipStream_t s, uint64_t *visits = nullptr, uint64_t *labels = nullptr);
 // the node protocol's error bits: 1 -> MBRWT_ERR_RANGE, 2 -> MBRWT_ERR_UNSUPPORTED (+ *msg for set_error)
 int node_error_code(uint64_t bits, const char **msg = nullptr);
 
@@ -717,24 +723,9 @@ inline bool pack_enabled() { return (build_tuning().node_kinds & 2u) != 0; }
 inline bool pack2_enabled() { return pack_enabled() && (build_tuning().node_kinds & 4u) != 0; }
 inline bool packt_enabled() { return pack_enabled() && (build_tuning().node_kinds & 8u) != 0; }
 
-// queries (query.hip)
-// column query (column.hip): ascending rows of `column` into d_rows (u64)
-int run_get_column(Ctx &c, uint64_t column, uint64_t *d_rows, uint64_t rows_cap, uint64_t *rows_needed,
-                   hipStream_t s);
-// batched column query (rows_columns.hip): the ascending rows
-// of [row_begin, row_end) per requested slot as a CSR, d_offsets (n_columns +
-// 1) complete also on MBRWT_ERR_CAPACITY.  `columns`: host, checked by the
-// caller (in range, no duplicate), null = every column in order.  stage !=
-// null: the rows go to stage->buf, grown to the total once it is known and
-// within rows_cap (the host form), instead of d_rows.
-int run_get_columns(Ctx &c, const uint64_t *columns, uint64_t n_columns, uint64_t row_begin, uint64_t row_end,
-                    uint64_t *d_offsets, uint64_t *d_rows, uint64_t rows_cap, uint64_t *rows_needed, Workspace *stage,
-                    hipStream_t s);
-const char *traverse_kernel_name(const Ctx &c);  // the kernel mbrwt_get_rows* launches
-// mbrwt_get_rows: host row ids -> host CSR, chunked and pipelined (hostpipe.cpp)
-// (width: bytes per label of cols, 4 or 2)
-int host_get_rows(Ctx &c, const uint64_t *rows, uint64_t n, uint64_t *offsets, void *cols, uint64_t cols_cap,
-                  uint64_t *cols_needed, uint32_t width = 4);
+// queries, by the file that defines them ---------------------------------
+// query.hip: the router -- row records, row shards or the node images
+// (kernels: nodes_walk.hpp)
 int run_get_rows(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offsets, uint32_t *d_cols, uint64_t cap,
                  uint64_t *needed, hipStream_t s);
 // u16 labels (mbrwt_get_rows16*): the row records' own narrow stores, else
@@ -745,8 +736,26 @@ int run_get_rows16(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_offse
                    uint64_t *needed, hipStream_t s);
 int run_get_batch(Ctx &c, const uint64_t *d_rows, const uint64_t *d_cols, uint64_t n, uint8_t *d_out, hipStream_t s);
 int run_count_labels(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *d_counts, hipStream_t s);
-// batched get_labels(indices, presence_ratio) (classify.hip)
-// the classify driver, shared by both schemes (classify.hip): the rows'
+int run_count_work(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *visits, uint64_t *labels, hipStream_t s);
+const char *traverse_kernel_name(const Ctx &c);  // the kernel mbrwt_get_rows* launches
+// column.hip: ascending rows of `column` into d_rows (u64)
+int run_get_column(Ctx &c, uint64_t column, uint64_t *d_rows, uint64_t rows_cap, uint64_t *rows_needed,
+                   hipStream_t s);
+// rows_columns.hip: the batched column query: the ascending rows
+// of [row_begin, row_end) per requested slot as a CSR, d_offsets (n_columns +
+// 1) complete also on MBRWT_ERR_CAPACITY.  `columns`: host, checked by the
+// caller (in range, no duplicate), null = every column in order.  stage !=
+// null: the rows go to stage->buf, grown to the total once it is known and
+// within rows_cap (the host form), instead of d_rows.
+int run_get_columns(Ctx &c, const uint64_t *columns, uint64_t n_columns, uint64_t row_begin, uint64_t row_end,
+                    uint64_t *d_offsets, uint64_t *d_rows, uint64_t rows_cap, uint64_t *rows_needed, Workspace *stage,
+                    hipStream_t s);
+// hostpipe.cpp: mbrwt_get_rows, host row ids -> host CSR, chunked and pipelined
+// (width: bytes per label of cols, 4 or 2)
+int host_get_rows(Ctx &c, const uint64_t *rows, uint64_t n, uint64_t *offsets, void *cols, uint64_t cols_cap,
+                  uint64_t *cols_needed, uint32_t width = 4);
+// classify.hip: batched get_labels(indices, presence_ratio)
+// the classify driver, shared by both schemes: the rows'
 // labels come from `get_rows` (device CSR; MBRWT_ERR_CAPACITY + need when
 // cols_cap is too small), workspaces from the scheme's context
 struct ClassifyIo {
@@ -765,6 +774,5 @@ int run_get_labels_batch(Ctx &c, const uint64_t *d_rows, uint64_t n_rows, const 
 int run_get_top_labels_batch(Ctx &c, const uint64_t *d_rows, uint64_t n_rows, const uint64_t *d_read_off,
                              uint64_t n_reads, uint64_t num_top, uint64_t *d_lab_off, uint32_t *d_labels,
                              uint64_t *d_counts, uint64_t cap, uint64_t *needed, hipStream_t s);
-int run_count_work(Ctx &c, const uint64_t *d_rows, uint64_t n, uint64_t *visits, uint64_t *labels, hipStream_t s);
 
 }  // namespace mbrwt

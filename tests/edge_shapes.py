@@ -148,7 +148,7 @@ def closed_form_ok(off, cols, counts, shifts=None):
     return np.array_equal(cols[order], want)
 
 
-# ---- the node-image fixtures (csrc/query.hip: 16-row rowblocks, 8-row chunks,
+# ---- the node-image fixtures (csrc/nodes_*.hip: 16-row rowblocks, 8-row chunks,
 # 256-row tiles; tests/test_gpu_node_edges.py) ---------------------------------
 
 def windows(m, top, shifts):

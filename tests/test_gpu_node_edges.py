@@ -1,4 +1,4 @@
-"""GPU parity of get_rows on the per-node images (csrc/query.hip) at the
+"""GPU parity of get_rows on the per-node images (csrc/query.hip and the csrc/nodes_*.hip kernel families) at the
 edges of their output path, on the deterministic fixtures of
 tests/edge_shapes.py.  The layout is pinned to 'nodes'; every config asserts
 its traversal kernel first; every comparison is bit-exact on integers, against
@@ -129,7 +129,7 @@ def _device(O, build_env, name):
 
 
 def _auto_slots(dev):
-    """auto_slots() of csrc/query.hip."""
+    """auto_slots() of csrc/nodes_walk.hpp."""
     mean = dev.num_relations() / dev.num_rows()
     k = 32
     while k < 2.0 * mean + 8.0 and k < 1024:

@@ -1,7 +1,8 @@
 """The option contract of MBRWT_OPT_KERNEL and the timing / status plumbing
 that the three get_rows drivers (node images, row records, variable-length
 records) share: values accepted and rejected, launches and milliseconds
-counted per call, return codes and messages of the ordinary API errors."""
+counted per call, return codes and messages of the ordinary API errors; the
+status protocol of the node-image point queries."""
 import ctypes as C
 
 import numpy as np
@@ -13,7 +14,7 @@ pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="n
 
 N, M, DENSITY, ARITY = 2000, 64, 0.05, 4
 RETIRED = set(range(2, 7)) | {10} | set(range(17, 21)) | set(range(24, 31))
-# the messages of csrc/query.hip, rows.hip and rows_var.hip
+# the messages of csrc/calls.cpp (shared by the node-image, rows.hip and rows_var.hip drivers)
 MSG_RANGE = "row out of range"
 MSG_CAPACITY = "cols_cap too small"
 
@@ -130,3 +131,84 @@ def test_timing_and_status_accounting(tree, build_env, kind):
     rc, need, msg = _get_rows_rc(d, rt, ot, ct, total - 1, s0)
     assert (rc, need, msg) == (L.MBRWT_ERR_CAPACITY, total, MSG_CAPACITY)
     sync_call()  # and a good call after them
+
+
+@pytest.mark.parametrize("ctx", ["group", "lane", "shards"])
+def test_node_point_queries_protocol(tree, build_env, ctx):
+    """get_batch, count_labels and the work count (V, L) on the node images
+    (the twin of test_gpu_edge_shapes.py test_point_queries_protocol): the
+    group kernel, the lane-per-row kernel and a row-sharded context; an empty
+    batch, one in-range row against the oracle, a batch whose last row is
+    num_rows (MBRWT_ERR_RANGE from all three calls), a good call afterwards."""
+    import torch
+    from genome_graph_annotation_amd import BRWTDevice, _lib as L
+    if ctx == "shards":
+        build_env("MBRWT_LAYOUT", "nodes")
+        build_env("MBRWT_SHARD_ROWS", "701")
+        dev = BRWTDevice.from_tree(tree.export())
+        assert dev.num_shards() == 3
+    else:
+        # without KIND_PACKT nodes the general kernel of variant 0 is k_traverse_group
+        # (a tree with them runs the lane-per-row kernel under both variants)
+        build_env("MBRWT_PACKT", "0")
+        dev = _dev(tree, "nodes")
+        dev.set_option(L.MBRWT_OPT_KERNEL, 1 if ctx == "lane" else 0)
+        if ctx == "lane":  # (variant 0: MODE_WORK and MODE_COUNT run k_traverse_group)
+            assert dev.traverse_kernel() == "k_traverse"
+    lib = L.lib()
+    assert dev.num_rows() == N and dev.num_columns() == M
+
+    def dev_rows(rows):
+        return torch.from_numpy(np.asarray(rows, dtype=np.uint64).view(np.int64)).cuda()
+
+    def get_batch(rows, cols):
+        rt, ct = dev_rows(rows), dev_rows(cols)
+        out = torch.full((max(1, len(rows)),), 7, dtype=torch.uint8, device="cuda")
+        st = lib.mbrwt_get_batch_device(dev._h, rt.data_ptr(), ct.data_ptr(), len(rows), out.data_ptr(), None)
+        torch.cuda.synchronize()
+        return st, out.cpu().numpy()
+
+    def count_labels(rows):
+        rt = dev_rows(rows)
+        cnt = torch.full((M,), 7, dtype=torch.int64, device="cuda")
+        st = lib.mbrwt_count_labels_device(dev._h, rt.data_ptr(), len(rows), cnt.data_ptr(), None)
+        torch.cuda.synchronize()
+        return st, cnt.cpu().numpy()
+
+    def count_work(rows):
+        rt = dev_rows(rows)
+        v, lab = C.c_uint64(2**64 - 1), C.c_uint64(2**64 - 1)
+        st = lib.mbrwt_count_work_device(dev._h, rt.data_ptr(), len(rows), C.byref(v), C.byref(lab), None)
+        return st, int(v.value), int(lab.value)
+
+    # n = 0
+    st, out = get_batch([], [])
+    assert st == L.MBRWT_OK and (out == 7).all()
+    st, cnt = count_labels([])
+    assert st == L.MBRWT_OK and (cnt == 0).all()
+    assert count_work([]) == (L.MBRWT_OK, 0, 0)
+    # one in-range row (past the first shard's rows) against the oracle
+    off_all, _ = tree.get_rows(np.arange(N, dtype=np.uint64))
+    r = 701 + int(np.argmax(np.diff(off_all.astype(np.int64))[701:] >= 3))
+    _, cols_o, vis = tree.get_rows(np.array([r], dtype=np.uint64), with_visits=True)
+    assert 3 <= len(cols_o) < M
+    bits_o = np.isin(np.arange(M), cols_o).astype(np.uint8)
+    st, out = get_batch([r] * M, np.arange(M))
+    assert st == L.MBRWT_OK
+    np.testing.assert_array_equal(out, bits_o)
+    st, cnt = count_labels([r])
+    assert st == L.MBRWT_OK
+    np.testing.assert_array_equal(cnt, bits_o.astype(np.int64))
+    assert count_work([r]) == (L.MBRWT_OK, int(vis.sum()), len(cols_o))
+    # the last row of the batch is num_rows
+    assert get_batch([r, 0, N], [0, 0, 0])[0] == L.MBRWT_ERR_RANGE
+    assert count_labels([r, 0, N])[0] == L.MBRWT_ERR_RANGE
+    assert count_work([r, 0, N])[0] == L.MBRWT_ERR_RANGE
+    # (and the context still answers)
+    st, out = get_batch([r] * M, np.arange(M))
+    assert st == L.MBRWT_OK
+    np.testing.assert_array_equal(out, bits_o)
+    st, cnt = count_labels([r, r])
+    assert st == L.MBRWT_OK
+    np.testing.assert_array_equal(cnt, 2 * bits_o.astype(np.int64))
+    assert count_work([r]) == (L.MBRWT_OK, int(vis.sum()), len(cols_o))
